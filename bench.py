@@ -7,10 +7,16 @@ x 4 096 B payload (8-B headers, one random key each, seed 42), packed
 contiguously, resident in HBM before timing starts. One step = one
 fws_gpu_unmask_sorted over one batch (a packed batch is sorted by
 construction; one launch, k_unmask_sorted, which finds each 4 KiB unit's
-frames itself). The any-order path fws_gpu_unmask_batch (k_plan +
-k_unmask_desc) is timed beside it in extra.C2_unmask_batch_any_order. Steps
-rotate over NBUF >= 4 distinct device copies (>= 1 GiB) so the 256 MiB
-Infinity Cache cannot serve a batch from the previous step.
+frames itself). Steps rotate over NBUF >= 4 distinct device copies (>= 1 GiB)
+so the 256 MiB Infinity Cache cannot serve a batch from the previous step.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the headline line. `--dump-outputs DIR` also writes what
+the last timed step left in its buffer (dump_outputs). Everything else is behind
+`--full`: the CPU baseline, the any-order path fws_gpu_unmask_batch (k_plan +
+k_unmask_desc) in extra.C2_unmask_batch_any_order, the other BASELINE configs
+and C1 echo in `extra`, and at N > 1 the C5 batch split; `--only`, `--no-cpu`,
+`--no-extra` and the like narrow a `--full` run.
 
 Multi-GPU: `bench.py --gpus N` (N > 1) started without torchrun's environment
 starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
@@ -18,12 +24,12 @@ child process before anything touches a GPU and exits with its code; under
 torchrun (the driver's launch) one rank per GPU. Every rank unmasks its own
 batch (independent frames, weak scaling, no collective on the data path); the
 timed region is bracketed by barrier + synchronize and the slowest rank's time
-is reported. At N > 1 the 8-GPU BASELINE config (C5: 4 GiB of 16 KiB TEXT
-frames per GPU, unmask + UTF-8 flags) is timed the same way -> extra.
+is reported. With `--full` at N > 1 the 8-GPU BASELINE config (C5: 4 GiB of
+16 KiB TEXT frames per GPU, unmask + UTF-8 flags) is timed the same way -> extra.
 
 Output: ONE JSON line on rank 0 (contract in the task statement), with
 `roofline` for the dominant kernel (k_unmask_sorted, timed live with HIP events on
-its stream) and `cpu_baseline` (the compiled reference's
+its stream) and, with `--full`, `cpu_baseline` (the compiled reference's
 WSocket::OnRecvData on this host, rank 0, N=1 only).
 """
 import argparse
@@ -52,9 +58,11 @@ EXTRA_WARM_S = 0.05            # and at least this long (s) of untimed calls bef
 HEAD_WARM_S = 0.25             # the headline's warmup: at least W calls and this long (s) of them
 EXTRA_CONFIGS = ("c2s", "c3", "dense", "c4", "tx", "c5s", "c5d", "e2e", "c1", "batch")
 C5_STREAM_STEPS = 16           # timed C5 stream calls, each on its own freshly masked 4 GiB buffer
-# rocprofv3 kernel stats of each extra config, captured warm (bench.py --only <cfg> under
+# rocprofv3 kernel stats of each extra config, captured warm (bench.py --full --only <cfg> under
 # rocprofv3 --kernel-trace --stats; tools/gpu_round.sh prof_extras)
 PROFILE_DIR = "profiles/r06"
+# --dump-outputs: block size, sampled blocks (x DUMP_BLOCK float32 = 32 MiB) and the sample's seed
+DUMP_BLOCK, DUMP_SAMPLE_BLOCKS, DUMP_SEED = 4096, 2048, 0xD0
 
 
 def parse():
@@ -65,16 +73,23 @@ def parse():
     ap.add_argument("--frames", type=int, default=65536)
     ap.add_argument("--payload", type=int, default=4096)
     ap.add_argument("--nbuf", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the reference's CPU baseline, the any-order comparison line, the "
+                         "other BASELINE configs, C1 echo and (N > 1) the C5 batch split. Without it a run sets up, "
+                         "warms up, times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step left in its batch buffer to "
+                         "DIR/*.npy (a fixed, seeded sample of 4 KiB blocks and the byte sum of every block)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-batch-extra", action="store_true",
-                    help="skip the fws_gpu_unmask_batch (plan + run) comparison line")
+                    help="with --full: skip the fws_gpu_unmask_batch (plan + run) comparison line")
     ap.add_argument("--extra", action="store_true",
-                    help="also time C2 stream decode, C3, C4, TX, e2e (PCIe) -> 'extra' "
+                    help="with --full: also time C2 stream decode, C3, C4, TX, e2e (PCIe) -> 'extra' "
                          "(default at N=1; multi-GPU runs time the headline only)")
     ap.add_argument("--c5", action="store_true", help="with --extra: the 4 GiB C5 UTF-8 config (default at N=1)")
-    ap.add_argument("--no-extra", action="store_true", help="headline line only")
-    ap.add_argument("--no-c5-split", action="store_true", help="N > 1: skip the C5 batch-split config")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra configs and the C1 echo")
+    ap.add_argument("--no-c5-split", action="store_true", help="with --full at N > 1: skip the C5 batch-split config")
     ap.add_argument("--share-device", action="store_true",
                     help="N > 1 validation on one GPU: every rank on device 0, gloo process group "
                          "(exercises the N-rank path on real HIP; not a scaling measurement)")
@@ -88,14 +103,22 @@ def parse():
                     help="CPU only (gloo): exercise the N-rank launch, barrier and max-over-ranks timing on a "
                          "host XOR of each rank's shard; prints a self-test line, not the metric")
     a = ap.parse_args()
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not a.no_extra:
-        a.extra = a.c5 = True
-    if a.no_extra:
-        a.extra = a.c5 = False
+    if a.steps < 1 or a.warmup < 0 or a.nbuf < 1:
+        ap.error("--steps and --nbuf must be at least 1, --warmup at least 0")
     a.only = {x.strip() for x in a.only.split(",") if x.strip()}
     bad = a.only - set(EXTRA_CONFIGS)
     if bad:
         ap.error(f"--only: unknown config(s) {sorted(bad)}; known: {EXTRA_CONFIGS}")
+    if not a.full:
+        if a.only or a.extra or a.c5:
+            ap.error("--only, --extra and --c5 choose among what --full runs: add --full")
+        # a plain run: the headline and nothing that takes a run of its own
+        a.no_cpu = a.no_batch_extra = a.no_extra = a.no_c5_split = True
+        return a
+    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not a.no_extra:
+        a.extra = a.c5 = True
+    if a.no_extra:
+        a.extra = a.c5 = False
     if a.only:
         a.extra = True
         a.c5 = bool(a.only & {"c5s", "c5d"})
@@ -351,6 +374,29 @@ def pmc_traffic():
     return (rec.get("hbm_bytes_per_launch") if current else None), src
 
 
+def dump_outputs(dirname, buf, rank=0, world=1):
+    """--dump-outputs: the batch buffer as the last timed step left it (headers in
+    place, payloads unmasked: what fws_gpu_unmask_sorted's caller has afterwards), cut
+    into DUMP_BLOCK-byte blocks, the tail zero-padded. Written as .npy:
+    block_byte_sums (float64, the byte sum of every block: the whole buffer) and
+    block_sample (float32, every byte of DUMP_SAMPLE_BLOCKS blocks picked with a fixed
+    seed, in buffer order; 32 MiB). At N > 1 every rank writes its own, *_rank<r>.
+    Returns the file names."""
+    os.makedirs(dirname, exist_ok=True)
+    out = buf.cpu().numpy()
+    nb = -(-len(out) // DUMP_BLOCK)
+    if nb * DUMP_BLOCK != len(out):
+        out = np.concatenate([out, np.zeros(nb * DUMP_BLOCK - len(out), dtype=np.uint8)])
+    blocks = out.reshape(nb, DUMP_BLOCK)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(nb, min(nb, DUMP_SAMPLE_BLOCKS), replace=False))
+    tag = f"_rank{rank}" if world > 1 else ""
+    arrays = {f"block_byte_sums{tag}": blocks.sum(axis=1, dtype=np.uint64).astype(np.float64),
+              f"block_sample{tag}": blocks[pick].astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(name + ".npy" for name in arrays)
+
+
 def launcher_selftest(args, world, rank):
     """CPU (gloo) rehearsal of the N-rank path: the same launch, shard seeds,
     barriers, max-over-ranks and aggregate as the GPU run, with a host XOR of
@@ -421,7 +467,18 @@ def main():
     # host-side CPU baseline and setup before it leave the GPU idle for tens of
     # seconds; the first ~100 launches after that run 1-5 % slower while the clocks
     # ramp up, profiles/r06/ab_*.jsonl first rounds)
-    _warm(lambda i: gpu.unmask_sorted(ctx, bufs[i % args.nbuf], dd, n), args.warmup, HEAD_WARM_S)
+    calls = _warm(lambda i: gpu.unmask_sorted(ctx, bufs[i % args.nbuf], dd, n), args.warmup, HEAD_WARM_S)
+    # The unmask is in place, so a call on an unmasked buffer masks it again, and how
+    # many warm-up calls ran depends on the clock. One more untimed call on each buffer
+    # that needs it leaves every buffer masked as generated, except that the last timed
+    # step's buffer is left so that this step finds it masked: the timed steps then see
+    # the same bytes in every run, and the last one's output is the unmasked batch.
+    last = (args.steps - 1) % args.nbuf
+    for j in range(args.nbuf):
+        done = len(range(j, calls, args.nbuf))
+        start_unmasked = j == last and len(range(j, args.steps, args.nbuf)) % 2 == 0
+        if done % 2 != int(start_unmasked):
+            gpu.unmask_sorted(ctx, bufs[j], dd, n)
 
     # ---- timed region: K whole steps. The dominant kernel (k_unmask_sorted, the
     # step's only launch) is timed by HIP events on its stream (the current
@@ -441,6 +498,7 @@ def main():
     own_s = (t1 - t0) / args.steps
     step_s = max_over_ranks(world, own_s)
     kern_s = min(ev0.elapsed_time(ev1) / 1e3 / args.steps, own_s)
+    dumped = dump_outputs(args.dump_outputs, bufs[last], rank, world) if args.dump_outputs else None
 
     extra = {}
     if not args.no_batch_extra and world == 1 and want(args, "batch"):
@@ -485,6 +543,8 @@ def main():
                      "alg_bytes_per_launch": alg_bytes},
     }
     out.update(extra)
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     if cpu is not None:
         out["cpu_baseline"] = cpu
     if rank == 0:
@@ -719,7 +779,8 @@ def _warm(fn, warmup=1, warm_s=EXTRA_WARM_S):
     """untimed calls in rounds of max(2, warmup) until both `warmup` calls and warm_s
     seconds have passed: a config whose timed region lasts a few ms otherwise runs
     on clocks still ramping up after the host-side setup before it (C4 measured
-    0.088 ms over its first 110 calls, 0.085 after; tools/c4_thermal_probe.py)"""
+    0.088 ms over its first 110 calls, 0.085 after; tools/c4_thermal_probe.py).
+    Returns the number of calls made."""
     i = 0
     t0 = time.perf_counter()
     while True:
@@ -728,7 +789,7 @@ def _warm(fn, warmup=1, warm_s=EXTRA_WARM_S):
             i += 1
         torch.cuda.synchronize()
         if i >= warmup and time.perf_counter() - t0 >= warm_s:
-            return
+            return i
 
 
 def _time(fn, steps, stream, warmup=1, warm_s=EXTRA_WARM_S):

@@ -120,3 +120,45 @@ def test_c5_stream_record_check_fails_loudly():
                 {"flags_match_generator": False}, {"checked_call_status": -1}, {"checked_call_frames": 5}):
         with pytest.raises(RuntimeError):
             bench.check_c5_stream({**good, **bad})
+
+
+def test_plain_run_is_headline_only(monkeypatch):
+    """bench.py without --full runs nothing beside the headline (no CPU baseline,
+    comparison line, extra config or C5 split); --full keeps the earlier defaults,
+    and the options that choose among its parts need it."""
+    import sys
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2
+    assert a.no_cpu and a.no_batch_extra and a.no_c5_split and not a.extra and not a.c5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert not a.no_cpu and not a.no_batch_extra and not a.no_c5_split and a.extra and a.c5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--only", "c4", "--no-cpu"])
+    a = bench.parse()
+    assert a.no_cpu and a.extra and not a.c5 and a.only == {"c4"}
+    for argv in (["--only", "c4"], ["--extra"], ["--c5"], ["--steps", "0"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
+def test_dump_outputs_blocks(tmp_path):
+    """bench.dump_outputs: the byte sum of every 4 KiB block of the buffer (the
+    tail zero-padded) as float64, and a fixed seeded pick of whole blocks as float32."""
+    import bench
+    import torch
+    buf = np.random.default_rng(3).integers(0, 256, 5 * bench.DUMP_BLOCK + 123, dtype=np.uint8)
+    names = bench.dump_outputs(str(tmp_path / "d"), torch.from_numpy(buf))
+    assert names == ["block_byte_sums.npy", "block_sample.npy"]
+    sums = np.load(tmp_path / "d" / "block_byte_sums.npy")
+    sample = np.load(tmp_path / "d" / "block_sample.npy")
+    assert sums.dtype == np.float64 and sample.dtype == np.float32
+    pad = np.concatenate([buf, np.zeros(bench.DUMP_BLOCK - 123, dtype=np.uint8)]).reshape(6, bench.DUMP_BLOCK)
+    assert np.array_equal(sums, pad.sum(axis=1))
+    assert np.array_equal(sample, pad)                             # fewer blocks than the sample: all, in order
+    again = bench.dump_outputs(str(tmp_path / "e"), torch.from_numpy(buf), rank=1, world=2)
+    assert again == ["block_byte_sums_rank1.npy", "block_sample_rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "e" / "block_sample_rank1.npy"), sample)

@@ -6,9 +6,9 @@
 # into profiles/$ROUND/).
 #   tests        pytest -m gpu (whole suite, one process)
 #   smoke        __graft_entry__.smoke()
-#   bench        python bench.py (default: headline + extras + C1 + CPU baseline)
-#   bench_quick  python bench.py --no-extra --no-cpu
-#   share2       bench.py --gpus 2 --share-device (two ranks on device 0, gloo): the N-rank path on HIP
+#   bench        python bench.py --full (headline + extras + C1 + CPU baseline)
+#   bench_quick  python bench.py (a plain run: the headline only)
+#   share2       bench.py --full --gpus 2 --share-device (two ranks on device 0, gloo): the N-rank path on HIP
 #   pmc          FETCH_SIZE / WRITE_SIZE passes of the headline kernel (separate runs)
 #   pmc_rq       the TCC_EA0_RDREQ 32/64/128-B request counts of the headline kernel (sized reads)
 #   prof_main    rocprofv3 kernel trace + stats of the headline bench
@@ -42,14 +42,14 @@ for step in "$@"; do
             || fail smoke $? "$O/smoke.log"
         tail -1 "$O/smoke.log" ;;
     bench)
-        timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || fail bench $? "$O/bench.err"
+        timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || fail bench $? "$O/bench.err"
         cut -c1-600 "$O/bench.json" ;;
     bench_quick)
-        timeout -k 10 300 python bench.py --no-extra --no-cpu > "$O/bench_quick.json" 2> "$O/bench_quick.err" \
+        timeout -k 10 300 python bench.py > "$O/bench_quick.json" 2> "$O/bench_quick.err" \
             || fail bench_quick $? "$O/bench_quick.err"
         cut -c1-600 "$O/bench_quick.json" ;;
     share2)
-        timeout -k 10 600 python bench.py --gpus 2 --share-device --no-cpu --steps 20 --warmup 5 \
+        timeout -k 10 600 python bench.py --full --gpus 2 --share-device --no-cpu --steps 20 --warmup 5 \
             > "$O/share2.json" 2> "$O/share2.err" || fail share2 $? "$O/share2.err"
         cut -c1-2000 "$O/share2.json" ;;
     pmc)
@@ -104,14 +104,14 @@ for step in "$@"; do
         tail -1 "$O/utf8_tests.log" ;;
     ab_c5)       # A/B: UTF-8 check forms (FWS_LIB_VARIANT=swar: make exp EXP_TAG=swar EXP_DEFS=-DFWS_UTF8_SWAR=1)
         for v in swar "" swar ""; do
-            FWS_LIB_VARIANT=$v timeout -k 10 300 python bench.py --only c5d,c5s --no-cpu --no-batch-extra --steps 20 --warmup 5 \
+            FWS_LIB_VARIANT=$v timeout -k 10 300 python bench.py --full --only c5d,c5s --no-cpu --no-batch-extra --steps 20 --warmup 5 \
                 >> "$O/ab_c5.jsonl" 2>> "$O/ab_c5.err" || fail ab_c5 $? "$O/ab_c5.err"
             python3 -c "import json,sys;d=json.loads(open('$O/ab_c5.jsonl').read().splitlines()[-1]);e=d['extra'];print('variant=${v:-product}', e['C5_utf8_descriptor']['ms_per_step'], e['C5_utf8_text_decode']['ms_per_step'])"
         done ;;
-    prof_extras)  # warm kernel stats per config: bench.py --only CFG under rocprofv3, stats of the timed window
+    prof_extras)  # warm kernel stats per config: bench.py --full --only CFG under rocprofv3, stats of the timed window
         mkdir -p "$O/profiles"
         for c in ${PROF_CFGS:-c3 dense c2s c4 tx c5d c5s}; do
-            prof "prof_$c" 400 --kernel-trace --stats -f csv -d "$O/prof_$c" -o run -- python3 "$R/bench.py" --only $c --no-cpu --no-batch-extra --no-pipelined --steps 20 --warmup 5
+            prof "prof_$c" 400 --kernel-trace --stats -f csv -d "$O/prof_$c" -o run -- python3 "$R/bench.py" --full --only $c --no-cpu --no-batch-extra --no-pipelined --steps 20 --warmup 5
             grep '^{"metric"' "$O/prof_$c.log" | tail -1 > "$O/profiles/${c}_bench_line.json"
             last=20; case $c in c5*) last=16 ;; esac
             python3 tools/prof_window.py "$O/prof_$c/run_kernel_trace.csv" --last $last --out "$O/profiles/${c}_kernel_stats.csv" \

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel stats over the timed window of a bench.py config run under rocprofv3
 (--kernel-trace): per kernel name, the last K dispatches (a config's timed
-calls come after its warm-up calls; run bench.py --only CFG --no-pipelined so
+calls come after its warm-up calls; run bench.py --full --only CFG --no-pipelined so
 nothing else follows them). Writes rocprofv3's stats columns for the window,
 plus the run's whole-run stats beside it, and prints a JSON summary.
 
