@@ -30,6 +30,7 @@ FWS_ERR_NOT_MASKED = -3
 FWS_ERR_MASKED = -4
 FWS_ERR_OPCODE = -9
 FWS_ERR_CONTROL_FRAME = -10
+FWS_ERR_SEQUENCE = -11
 FWS_ERR_CAPACITY = -20
 FWS_ERR_INVALID = -21
 FWS_ERR_NO_DEVICE = -22
@@ -44,6 +45,12 @@ FRAME_INFO = np.dtype([("hdr_off", "<u8"), ("payload_len", "<u8"), ("key", "<u4"
 DECODE_RESULT = np.dtype([("status", "<i4"), ("n_frames", "<u4"), ("consumed", "<u8"),
                           ("err_off", "<u8"), ("carry_unread", "<u8"), ("carry_hdr_len", "<u4"),
                           ("n_survivors", "<u4")])
+MSG_INFO = np.dtype([("off", "<u8"), ("len", "<u8"), ("first_frame", "<u4"), ("last_frame", "<u4"),
+                     ("n_data_frames", "<u4"), ("opcode", "u1"), ("utf8_ok", "u1"), ("flags", "u1"), ("pad", "u1")])
+MSG_RESULT = np.dtype([("status", "<i4"), ("n_msgs", "<u4"), ("err_frame", "<u4"), ("open_first_frame", "<u4"),
+                       ("open_opcode", "<u4"), ("n_data_frames", "<u4"), ("data_bytes", "<u8"),
+                       ("ctl_bytes", "<u8"), ("open_off", "<u8"), ("open_len", "<u8"), ("resume_off", "<u8")])
+assert MSG_INFO.itemsize == 32 and MSG_RESULT.itemsize == 64
 RX_EVENT = np.dtype([("kind", "<u4"), ("opcode", "<u4"), ("is_ctl", "u1"), ("frame_end", "u1"),
                      ("msg_end", "u1"), ("fin", "u1"), ("code", "<u4"), ("size", "<u8"),
                      ("data_off", "<u8"), ("ctl_off", "<u8"), ("capacity", "<u8")])
@@ -93,6 +100,7 @@ SIGNATURES = [
     ("fws_gpu_unmask_run", _I, [_P, _P, _P, _U32, _P]),
     ("fws_gpu_unmask_gather", _I, [_P, _P, _P, _P, _U32, _P]),
     ("fws_gpu_decode_stream", _I, [_P, _P, _U64, _P, _U32, _P, _P, _P]),
+    ("fws_gpu_decode_messages", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P]),
     ("fws_gpu_validate_utf8", _I, [_P, _P, _P, _U32, _P, _P]),
     ("fws_rx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_rx_session_destroy", None, [_P]),

@@ -71,6 +71,28 @@ int fws_ctx_ensure_seam(fws_gpu_ctx *ctx, uint64_t span) {
     return 0;
 }
 
+// the message planner's workspace for `frames` frames (fws_gpu_decode_messages)
+int fws_ctx_ensure_msg(fws_gpu_ctx *ctx, uint64_t frames) {
+    fws_msg_ws &m = ctx->msg;
+    if (frames <= m.cap && m.descs) return 0;
+    if (frames < m.cap) frames = m.cap;
+    dev_free(m.descs);
+    dev_free(m.ctl_off);
+    dev_free(m.agg);
+    dev_free(m.pre);
+    m.cap = 0;
+    int r;
+    if ((r = dev_alloc(&m.descs, frames + 1))) return r;
+    if ((r = dev_alloc(&m.ctl_off, frames + 1))) return r;
+    if ((r = dev_alloc(&m.agg, 8 * (frames / 256 + 2)))) return r;
+    if ((r = dev_alloc(&m.pre, 8 * (frames / 256 + 2)))) return r;
+    if ((r = fws_hip_status(hipMemset(m.agg, 0, 8 * (frames / 256 + 2) * 8)))) return r;
+    if ((r = fws_hip_status(hipMemset(m.pre, 0, 8 * (frames / 256 + 2) * 8)))) return r;
+    m.cap = frames;
+    m.last_epoch = 0;
+    return 0;
+}
+
 extern "C" {
 
 // Test / tuning hook (not part of the ABI): the decode counters of the last
@@ -86,6 +108,21 @@ __attribute__((visibility("default"))) int fws_internal_decode_counters(fws_gpu_
 __attribute__((visibility("default"))) int fws_internal_plan_mode(fws_gpu_ctx *ctx, uint64_t *out5) {
     if (!ctx || !out5 || !ctx->plan.mode) return FWS_ERR_INVALID;
     return fws_hip_status(hipMemcpy(out5, ctx->plan.mode, 5 * 8, hipMemcpyDeviceToHost));
+}
+
+// Timing hook (not part of the ABI; tools/msg_bench.py): the parse of
+// fws_gpu_decode_stream / fws_gpu_decode_messages alone -- scan + resolve into
+// dev_frames / *dev_result, nothing unmasked.
+__attribute__((visibility("default"))) int fws_internal_decode_parse(fws_gpu_ctx *ctx, const void *dev_wire,
+                                                                     uint64_t len, fws_frame_info *dev_frames,
+                                                                     uint32_t cap, fws_decode_result *dev_result,
+                                                                     void *stream) {
+    if (!ctx || !dev_result || (len && !dev_wire) || (cap && !dev_frames) || ((uintptr_t)dev_wire & 15u))
+        return FWS_ERR_INVALID;
+    int r;
+    if ((r = fws_hip_status(hipSetDevice(ctx->device))) || (r = fws_decode_prepare(ctx, len, cap, false))) return r;
+    return fws_launch_decode(ctx, (uint8_t *)const_cast<void *>(dev_wire), len, dev_frames, cap, dev_result, nullptr,
+                             (hipStream_t)stream);
 }
 
 int fws_gpu_abi_version(void) { return FWS_GPU_ABI_VERSION; }
@@ -148,6 +185,10 @@ void fws_gpu_ctx_destroy(fws_gpu_ctx *ctx) {
     dev_free(d.bg_sc);
     dev_free(d.bg_mark);
     dev_free(ctx->seam);
+    dev_free(ctx->msg.descs);
+    dev_free(ctx->msg.ctl_off);
+    dev_free(ctx->msg.agg);
+    dev_free(ctx->msg.pre);
     delete ctx;
 }
 
@@ -158,6 +199,11 @@ int fws_gpu_ctx_reserve(fws_gpu_ctx *ctx, uint64_t max_frames, uint64_t max_stre
     // chunks <= bytes / 16 + 2 per frame; units = chunks / 256
     const uint64_t units = (max_stream_bytes / 16 + 2 * max_frames) / 256 + 2;
     if ((r = fws_ctx_ensure_plan(ctx, max_frames, units))) return r;
+    // fws_gpu_decode_messages after a reservation never allocates: its parse's
+    // workspace and the message planner's are sized here too
+    const uint32_t fcap = max_frames < 0xFFFFFFFFull ? (uint32_t)max_frames : 0xFFFFFFFFu;
+    if ((r = fws_decode_ensure(ctx, max_stream_bytes, fcap))) return r;
+    if ((r = fws_ctx_ensure_msg(ctx, max_frames))) return r;
     if (max_stream_bytes > ctx->cap_stream) ctx->cap_stream = max_stream_bytes;
     return fws_ctx_ensure_seam(ctx, ctx->cap_stream);
 }
@@ -331,6 +377,61 @@ int fws_gpu_decode_stream(fws_gpu_ctx *ctx, void *dev_wire, uint64_t len, fws_fr
     if ((r = fws_launch_decode(ctx, (uint8_t *)dev_wire, len, dev_frames, cap, dev_result, dev_utf8_ok, s)))
         return r;
     return fws_decode_unmask(ctx, (uint8_t *)dev_wire, len, dev_frames, cap, dev_utf8_ok, s);
+}
+
+int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len, fws_frame_info *dev_frames,
+                            uint32_t cap, fws_msg_info *dev_msgs, uint32_t msg_cap, void *dev_dst, uint64_t dst_cap,
+                            void *dev_ctl, uint64_t ctl_cap, fws_decode_result *dev_result,
+                            fws_msg_result *dev_msg_result, void *stream) {
+    if (!ctx || !dev_result || !dev_msg_result || (len && !dev_wire) || (cap && !dev_frames) ||
+        (msg_cap && !dev_msgs) || (dst_cap && !dev_dst) || (ctl_cap && !dev_ctl))
+        return FWS_ERR_INVALID;
+    if ((((uintptr_t)dev_wire | (uintptr_t)dev_dst) & 15u) != 0) return FWS_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    // the parse never writes the wire (k_scan and the resolve read it); its launchers
+    // share fws_gpu_decode_stream's pointer type
+    uint8_t *const wire = (uint8_t *)const_cast<void *>(dev_wire);
+    int r;
+    if ((r = fws_hip_status(hipSetDevice(ctx->device)))) return r;
+    if ((r = fws_decode_prepare(ctx, len, cap, false)) || (r = fws_ctx_ensure_msg(ctx, cap))) return r;
+    // Captured into a graph, the call is replayed with the arguments of this one
+    // launch sequence: the counter set and the look-back epochs that eager calls
+    // alternate / advance on the host are then the same at every replay. So a
+    // captured call records the two resets itself (memset nodes on the same
+    // chain): its counter set, and the look-back words the planner and the gather
+    // plan tag.
+    bool capturing = false;
+    if (s) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if ((r = fws_hip_status(hipStreamIsCapturing(s, &cs)))) return r;
+        capturing = cs == hipStreamCaptureStatusActive;
+    }
+    if (capturing) {
+        ctx->dec.cnt_dirty = true;
+        if ((r = fws_hip_status(hipMemsetAsync(ctx->plan.status, 0, ctx->plan.status_cap * 8, s)))) return r;
+    }
+    r = fws_launch_decode(ctx, wire, len, dev_frames, cap, dev_result, nullptr, s);
+    if (capturing) ctx->dec.cnt_dirty = true;          // the other set is zeroed only when the graph runs
+    if (r) return r;
+    // the resolve left the device frame count; its stream-space unmask plan in
+    // ctx->plan is not used (no in-place unmask follows): the planner's look-back
+    // and the gather plan take that workspace over
+    const uint32_t *n_dev = ctx->dec.counters + kDecodeFramesCounter;
+    if ((r = fws_launch_msg_plan(ctx, len, dev_frames, cap, n_dev, dev_result, dev_msgs, msg_cap, dst_cap, ctl_cap,
+                                 dev_msg_result, capturing, s)))
+        return r;
+    // unmask + compaction in one pass: the gather over the planner's cap descriptors
+    // (the data frames' payloads with their keys, then zero-length regions)
+    if (cap && dst_cap) {
+        const uint64_t max_bytes = len < dst_cap ? len : dst_cap;
+        if ((r = fws_launch_gather((uint8_t *)dev_dst, wire, ctx->msg.descs, cap, ctx->plan, max_bytes, s, dst_cap)))
+            return r;
+    }
+    if (ctl_cap && (r = fws_launch_msg_ctl(ctx, wire, dev_frames, cap, n_dev, dev_msg_result, (uint8_t *)dev_ctl,
+                                           ctl_cap, s)))
+        return r;
+    if (cap && dst_cap) return fws_launch_utf8_msgs((const uint8_t *)dev_dst, dev_msgs, msg_cap, dev_msg_result, dst_cap, s);
+    return 0;
 }
 
 }  // extern "C"

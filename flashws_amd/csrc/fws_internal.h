@@ -225,6 +225,16 @@ struct fws_decode_ws {
     uint32_t *bg_mark = nullptr;           // [max_nodes] k_emit: on the path
 };
 
+// Message-planner workspace (msg_kernels.hip), sized by the frame capacity.
+struct fws_msg_ws {
+    uint64_t cap = 0;                 // frames
+    fws_frame_desc *descs = nullptr;  // [cap] the data frames' payload regions, compacted; zero-length after them
+    uint64_t *ctl_off = nullptr;      // [cap] per frame: its payload's offset in dev_ctl, or ~0
+    uint64_t *agg = nullptr;          // [cap / 256 + 2][8] look-back words (zeroed): a workgroup's scan aggregate
+    uint64_t *pre = nullptr;          // [cap / 256 + 2][8]            and its inclusive prefix
+    uint32_t last_epoch = 0;          // the plan epoch of the last k_msg_plan (its tags in agg / pre)
+};
+
 struct fws_gpu_ctx {
     int device = 0;
     uint64_t cap_frames = 0;
@@ -232,6 +242,7 @@ struct fws_gpu_ctx {
     uint64_t cap_stream = 0;
     fws_plan_ws plan;
     fws_decode_ws dec;
+    fws_msg_ws msg;
     void *pinned = nullptr;           // host staging for small readbacks
     uint32_t *seam = nullptr;         // fws_gpu_unmask_sorted_utf8: first / last unmasked dword per unit
     uint64_t seam_cap = 0;            // words
@@ -246,6 +257,7 @@ int fws_ctx_ensure_seam(fws_gpu_ctx *ctx, uint64_t span);
 int fws_ctx_ensure_any(fws_gpu_ctx *ctx);             // the piece queue, sized from the reservation
 
 int fws_ctx_ensure_plan(fws_gpu_ctx *ctx, uint64_t frames, uint64_t units);
+int fws_ctx_ensure_msg(fws_gpu_ctx *ctx, uint64_t frames);   // the message planner's workspace
 
 // unmask_kernels.hip
 int fws_launch_mask_single(void *dev_ptr, uint64_t n, uint32_t key, uint32_t phase, hipStream_t s);
@@ -280,15 +292,32 @@ int fws_launch_unmask_stream(uint8_t *base, uint64_t N, const fws_frame_info *fr
 
 // outplan_kernels.hip: one-launch output-space plans (base = ws.cbase, unit map, total)
 int fws_plan_next_epoch(fws_plan_ws &ws, hipStream_t s);
-int fws_launch_gather_plan(const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws, hipStream_t s);
+// out_cap: a total above it plans nothing (*ws.total = 0: the gather writes nothing)
+int fws_launch_gather_plan(const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws, hipStream_t s,
+                           uint64_t out_cap = ~0ull);
 int fws_launch_tx_plan(const fws_tx_desc *d, uint32_t n, fws_plan_ws &ws, uint64_t out_cap, uint64_t *out_len,
                        hipStream_t s);
 
 // text_kernels.hip
 int fws_launch_utf8_descs(const uint8_t *base, const fws_frame_desc *descs, uint32_t n, uint8_t *ok,
                           hipStream_t s);
+// dst_cap: regions whose total exceeds it are not gathered at all (plan + k_gather_fast only)
 int fws_launch_gather(uint8_t *dst, const uint8_t *src, const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws,
-                      uint64_t max_bytes, hipStream_t s);
+                      uint64_t max_bytes, hipStream_t s, uint64_t dst_cap = ~0ull);
+// UTF-8 verdicts of the completed TEXT entries of msgs[0, min(res->n_msgs, msg_cap)) over their
+// regions of dst (fws_gpu_decode_messages); none when res->data_bytes exceeds dst_cap
+int fws_launch_utf8_msgs(const uint8_t *dst, fws_msg_info *msgs, uint32_t msg_cap, const fws_msg_result *res,
+                         uint64_t dst_cap, hipStream_t s);
+
+// msg_kernels.hip: the message planner over the decoded frame list (n_dev frames, <= cap): the
+// compacted data-frame descriptors in ctx->msg.descs[0, cap), msgs, *out (reset: zero the look-back
+// words first, for a call whose launches are replayed); then the control payloads
+int fws_launch_msg_plan(fws_gpu_ctx *ctx, uint64_t len, const fws_frame_info *frames, uint32_t cap,
+                        const uint32_t *n_dev, const fws_decode_result *res, fws_msg_info *msgs, uint32_t msg_cap,
+                        uint64_t dst_cap, uint64_t ctl_cap, fws_msg_result *out, bool reset, hipStream_t s);
+int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
+                       const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
+                       hipStream_t s);
 
 // decode_kernels.hip
 constexpr int kDecodeFramesCounter = 3;   // index of the device frame count in dec.counters

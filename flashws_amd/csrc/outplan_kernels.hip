@@ -44,8 +44,8 @@ static int launch_out_plan(const Desc *d, uint32_t n, fws_plan_ws &ws, uint64_t 
     return fws_hip_status(hipGetLastError());
 }
 
-int fws_launch_gather_plan(const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws, hipStream_t s) {
-    return launch_out_plan(d, n, ws, ~0ull, nullptr, s);
+int fws_launch_gather_plan(const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws, hipStream_t s, uint64_t out_cap) {
+    return launch_out_plan(d, n, ws, out_cap, nullptr, s);
 }
 
 int fws_launch_tx_plan(const fws_tx_desc *d, uint32_t n, fws_plan_ws &ws, uint64_t out_cap, uint64_t *out_len,

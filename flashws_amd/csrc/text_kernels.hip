@@ -66,6 +66,42 @@ __global__ __launch_bounds__(kBlock) void k_utf8(const uint8_t *__restrict__ bas
     }
 }
 
+// k_utf8 over reassembled messages (fws_gpu_decode_messages): the regions are
+// the completed TEXT entries of msgs[0, min(res->n_msgs, msg_cap)) in dst, the
+// count read on the device; the verdict goes to the entry's utf8_ok (the
+// planner preset every entry's to 0; other entries are left alone). Nothing is
+// checked when the data bytes did not fit dst (nothing was gathered).
+__global__ __launch_bounds__(kBlock) void k_utf8_msgs(const uint8_t *__restrict__ dst, fws_msg_info *__restrict__ msgs,
+                                                      uint32_t msg_cap, const fws_msg_result *__restrict__ res,
+                                                      uint64_t dst_cap) {
+    uint32_t n = res->n_msgs;
+    if (n > msg_cap) n = msg_cap;
+    if (res->data_bytes > dst_cap) return;
+    const int lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * (kBlock / 64);
+    for (uint32_t f = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); f < n; f += nw) {
+        if (msgs[f].opcode != 1u) continue;
+        const uintptr_t lo = (uintptr_t)(dst + msgs[f].off), hi = lo + msgs[f].len;
+        uint32_t bad = 0, carry = 0;
+        for (uintptr_t w0 = lo & ~uintptr_t(15); w0 < hi + 3u; w0 += 1024u) {
+            const uintptr_t w = w0 + uintptr_t(lane) * 16u;
+            u32x4 v{0u, 0u, 0u, 0u};
+            if (w < hi) v = gload16(w);
+            v.x &= sel_bytes(w, lo, hi);
+            v.y &= sel_bytes(w + 4u, lo, hi);
+            v.z &= sel_bytes(w + 8u, lo, hi);
+            v.w &= sel_bytes(w + 12u, lo, hi);
+            uint32_t prev = __shfl_up(v.w, 1, 64);
+            if (lane == 0) prev = carry;
+            carry = __shfl(v.w, 63, 64);
+            if (w < hi + 3u && ((v.x | v.y | v.z | v.w | prev) & 0x80808080u))
+                bad |= utf8_err(v.x, prev) | utf8_err(v.y, v.x) | utf8_err(v.z, v.y) | utf8_err(v.w, v.z);
+        }
+        const bool ok = !__any(bad != 0);
+        if (lane == 0) msgs[f].utf8_ok = ok ? 1 : 0;
+    }
+}
+
 // ------------------------------------------------------------------ gather
 // Out-of-place reassembly of a fragmented message (C4): dst byte space = the
 // payload regions concatenated (dbase = exclusive prefix of payload_len), each
@@ -600,6 +636,15 @@ int fws_launch_utf8_descs(const uint8_t *base, const fws_frame_desc *descs, uint
     return fws_hip_status(hipGetLastError());
 }
 
+int fws_launch_utf8_msgs(const uint8_t *dst, fws_msg_info *msgs, uint32_t msg_cap, const fws_msg_result *res,
+                         uint64_t dst_cap, hipStream_t s) {
+    if (msg_cap == 0) return 0;
+    uint32_t blocks = (msg_cap + 3) / 4;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_utf8_msgs, dim3(blocks), dim3(kBlock), 0, s, dst, msgs, msg_cap, res, dst_cap);
+    return fws_hip_status(hipGetLastError());
+}
+
 // k_gather_one's grid: 4 x the resident workgroups (each builds the prefix
 // once; a grid-stride loop over units, 2-3 per wave on C4): fewer workgroups
 // leave a static tail (1 x resident: 0.095 ms on C4), more repeat the prefix
@@ -672,9 +717,9 @@ extern "C" __attribute__((visibility("default"))) uint64_t fws_internal_gather_o
 }
 
 int fws_launch_gather(uint8_t *dst, const uint8_t *src, const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws,
-                      uint64_t max_bytes, hipStream_t s) {
+                      uint64_t max_bytes, hipStream_t s, uint64_t dst_cap) {
     if (n == 0) return 0;
-    if (g_gather_one && n <= kGatherLdsMax) {
+    if (g_gather_one && n <= kGatherLdsMax && dst_cap == ~0ull) {
         uint64_t blocks = 0;
         const int r = gather_one_grid(max_bytes, &blocks);
         if (r != 0) return r;
@@ -684,7 +729,7 @@ int fws_launch_gather(uint8_t *dst, const uint8_t *src, const fws_frame_desc *d,
         if (e != hipSuccess) return fws_hip_status(e);
         return fws_hip_status(hipGetLastError());
     }
-    int r = fws_launch_gather_plan(d, n, ws, s);
+    int r = fws_launch_gather_plan(d, n, ws, s, dst_cap);
     if (r) return r;
     uint64_t units = max_bytes / kGatherUnit + 1;
     if (units > ws.unit_cap) units = ws.unit_cap;

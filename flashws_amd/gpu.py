@@ -9,7 +9,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DECODE_JOB, FRAME_DESC, FRAME_INFO, DECODE_RESULT, RX_EVENT, TX_DESC, GenParams, check, lib
+from ._lib import (DECODE_JOB, FRAME_DESC, FRAME_INFO, DECODE_RESULT, MSG_INFO, MSG_RESULT, RX_EVENT, TX_DESC,
+                   GenParams, check, lib)
 
 
 def _stream_handle(stream=None):
@@ -167,6 +168,40 @@ def decode_stream(ctx, wire, cap, frames=None, result=None, utf8_ok=None, stream
     rc = lib().fws_gpu_decode_stream(ctx.h, _ptr(wire), n, _ptr(frames), cap, _ptr(result), u,
                                      _stream_handle(stream))
     return rc, frames, result, utf8_ok
+
+
+def decode_messages(ctx, wire, cap, msg_cap, dst, ctl, frames=None, msgs=None, result=None, msg_result=None,
+                    stream=None, n=None, dst_cap=None, ctl_cap=None):
+    """fws_gpu_decode_messages on a device uint8 tensor: the stream's frames
+    grouped into messages, data payloads unmasked into dst (16-B aligned),
+    control payloads into ctl; wire is not modified. dst_cap / ctl_cap default
+    to the tensors' sizes. Returns (status, frames, msgs, result, msg_result)
+    -- device tensors, nothing synchronised."""
+    dev = wire.device
+    if frames is None:
+        frames = torch.empty(max(cap, 1) * FRAME_INFO.itemsize, dtype=torch.uint8, device=dev)
+    if msgs is None:
+        msgs = torch.empty(max(msg_cap, 1) * MSG_INFO.itemsize, dtype=torch.uint8, device=dev)
+    if result is None:
+        result = torch.empty(DECODE_RESULT.itemsize, dtype=torch.uint8, device=dev)
+    if msg_result is None:
+        msg_result = torch.empty(MSG_RESULT.itemsize, dtype=torch.uint8, device=dev)
+    n = wire.numel() if n is None else n
+    dst_cap = dst.numel() if dst_cap is None else dst_cap
+    ctl_cap = ctl.numel() if ctl_cap is None else ctl_cap
+    rc = lib().fws_gpu_decode_messages(ctx.h, _ptr(wire), n, _ptr(frames), cap, _ptr(msgs), msg_cap, _ptr(dst),
+                                       dst_cap, _ptr(ctl), ctl_cap, _ptr(result), _ptr(msg_result),
+                                       _stream_handle(stream))
+    return rc, frames, msgs, result, msg_result
+
+
+def read_msg_result(msg_result):
+    return np.frombuffer(msg_result.cpu().numpy().tobytes(), dtype=MSG_RESULT)[0]
+
+
+def read_messages(msgs, count):
+    raw = msgs[:count * MSG_INFO.itemsize].cpu().numpy()
+    return np.frombuffer(raw.tobytes(), dtype=MSG_INFO).copy()
 
 
 class DecodeEngine:

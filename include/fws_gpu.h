@@ -43,7 +43,12 @@ enum {
     FWS_ERR_CONTROL_FRAME = -10,/* host RX session: control frame with payload > 125 B
                                    (RFC 6455 §5.5). The reference does not check
                                    (only a debug FWS_ASSERT, w_socket.h:654) and overflows
-                                   its control buffer; the session refuses the frame. */
+                                   its control buffer; the session refuses the frame.
+                                   fws_gpu_decode_messages: the same, and a control frame
+                                   with FIN = 0. */
+    FWS_ERR_SEQUENCE = -11,     /* fws_gpu_decode_messages: a continuation frame with no message
+                                   open, or a TEXT / BIN frame while one is open (RFC 6455
+                                   §5.4). The reference does not check. */
     FWS_ERR_CAPACITY = -20,     /* an output array is too small (count still reported) */
     FWS_ERR_INVALID = -21,      /* bad argument / not initialised */
     FWS_ERR_NO_DEVICE = -22,    /* no gfx950 device visible */
@@ -190,6 +195,86 @@ int fws_gpu_unmask_gather(fws_gpu_ctx *ctx, void *dev_dst, const void *dev_src,
 int fws_gpu_decode_stream(fws_gpu_ctx *ctx, void *dev_wire, uint64_t len,
                           fws_frame_info *dev_frames, uint32_t cap,
                           fws_decode_result *dev_result, uint8_t *dev_utf8_ok, void *stream);
+
+/* ---- stream decode into messages ------------------------------------------
+ * What a WebSocket application consumes: whole messages, reassembled from
+ * their fragments (RFC 6455 §5.4), TEXT ones checked for UTF-8 (§8.1), control
+ * frames apart from the data they interrupt (§5.5). One entry per completed
+ * unit, in completion order -- the order an application's callback would see:
+ * a data message at its FIN frame, a control frame at its own position (a PING
+ * between two fragments comes before the message it interrupts). */
+typedef struct fws_msg_info {
+    uint64_t off;           /* data: offset in dev_dst; control: offset in dev_ctl */
+    uint64_t len;
+    uint32_t first_frame;   /* index into dev_frames */
+    uint32_t last_frame;
+    uint32_t n_data_frames; /* fragments of the message (control: 1) */
+    uint8_t opcode;         /* 1 TEXT, 2 BIN, 8 CLOSE, 9 PING, 10 PONG */
+    uint8_t utf8_ok;        /* TEXT message: 1 iff the reassembled bytes are well-formed UTF-8; else 0 */
+    uint8_t flags;          /* 0 */
+    uint8_t pad;
+} fws_msg_info;             /* 32 bytes */
+
+typedef struct fws_msg_result {
+    int32_t status;         /* see fws_gpu_decode_messages */
+    uint32_t n_msgs;        /* entries produced, also past msg_cap */
+    uint32_t err_frame;     /* frame index of a sequencing error (else 0xFFFFFFFF) */
+    uint32_t open_first_frame; /* first frame of the unfinished last message, 0xFFFFFFFF if none */
+    uint32_t open_opcode;   /* 1 / 2, 0 if none */
+    uint32_t n_data_frames; /* data frames placed in dev_dst */
+    uint64_t data_bytes;    /* bytes placed in dev_dst, open message included */
+    uint64_t ctl_bytes;     /* bytes placed in dev_ctl */
+    uint64_t open_off;      /* dev_dst offset and length of the open message's present bytes */
+    uint64_t open_len;
+    uint64_t resume_off;    /* wire offset to resubmit from: the open message's first header,
+                               else the end of the last frame processed */
+} fws_msg_result;           /* 64 bytes */
+
+/* fws_gpu_decode_stream's parse of a server-side wire stream dev_wire[0..len)
+ * that starts at a frame header, followed on the device by the grouping of its
+ * frames into messages, their out-of-place unmask and the UTF-8 check of the
+ * reassembled TEXT messages. dev_wire is not modified; dev_frames and
+ * *dev_result are what fws_gpu_decode_stream reports for the same bytes (the
+ * first min(n_frames, cap) frames are grouped). Asynchronous on `stream`, no
+ * host synchronisation, no device-to-host copy, and no allocation once
+ * fws_gpu_ctx_reserve has sized the context. dev_wire and dev_dst are 16-B
+ * aligned; dev_ctl may have any alignment.
+ *   dev_dst   the unmasked payloads of the data frames (opcodes 0, 1, 2) in
+ *             wire order: every message is one contiguous run, messages are
+ *             packed back to back, the bytes present of an unfinished last
+ *             message come last. If they exceed dst_cap nothing is written to
+ *             dev_dst (FWS_ERR_CAPACITY; data_bytes is still reported, and no
+ *             message gets a utf8_ok verdict).
+ *   dev_ctl   the unmasked payloads of the complete control frames (opcodes 8,
+ *             9, 10) packed in wire order (the ctl_out / ctl_off convention of
+ *             fws_rx_session_feed); the same rule against ctl_cap.
+ *   dev_msgs  entries [0, min(n_msgs, msg_cap)).
+ * A truncated last payload contributes the bytes present and completes
+ * nothing: a message whose FIN frame is truncated stays open, a truncated
+ * control frame is neither listed nor copied. An unfinished message never gets
+ * a utf8_ok verdict; the caller resubmits from resume_off.
+ * status is the earliest problem in wire order:
+ *   1. a sequencing error at frame e (err_frame = e): FWS_ERR_SEQUENCE for a
+ *      continuation with no message open or a TEXT / BIN frame while one is
+ *      open, FWS_ERR_CONTROL_FRAME for a control frame with FIN = 0 or a
+ *      payload over 125 B. Frames e and later are neither gathered nor listed;
+ *      the entries and bytes before e are delivered (as OnRecvData delivers
+ *      what precedes an error) and the open-message fields describe the state
+ *      just before e;
+ *   2. else the parse's own status from *dev_result;
+ *   3. else FWS_ERR_CAPACITY when n_frames > cap, n_msgs > msg_cap or a byte
+ *      capacity was exceeded;
+ *   4. else 0.
+ * Out of scope: carrying an open message and its UTF-8 state across calls,
+ * UTF-8 validation of CLOSE reasons, client-side streams, the C++ adapter and
+ * the FLoop hook. */
+int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len,
+                            fws_frame_info *dev_frames, uint32_t cap,
+                            fws_msg_info *dev_msgs, uint32_t msg_cap,
+                            void *dev_dst, uint64_t dst_cap,
+                            void *dev_ctl, uint64_t ctl_cap,
+                            fws_decode_result *dev_result, fws_msg_result *dev_msg_result,
+                            void *stream);
 
 /* ---- batched stream decode: many independent streams ----------------------
  * fws_gpu_decode_stream over a list of independent streams (the buffers of
