@@ -51,6 +51,11 @@ MSG_RESULT = np.dtype([("status", "<i4"), ("n_msgs", "<u4"), ("err_frame", "<u4"
                        ("open_opcode", "<u4"), ("n_data_frames", "<u4"), ("data_bytes", "<u8"),
                        ("ctl_bytes", "<u8"), ("open_off", "<u8"), ("open_len", "<u8"), ("resume_off", "<u8")])
 assert MSG_INFO.itemsize == 32 and MSG_RESULT.itemsize == 64
+FWS_MSG_CONTINUED = 1   # fws_msg_info.flags (fws_gpu_decode_messages_carry)
+MSG_CARRY = np.dtype([("open_opcode", "<u4"), ("open_frames", "<u4"), ("open_bytes", "<u8"), ("utf8_tail", "<u4"),
+                      ("utf8_bad", "<u4"), ("prev_open_opcode", "<u4"), ("prev_open_frames", "<u4"),
+                      ("prev_open_bytes", "<u8"), ("wire_bytes", "<u8"), ("n_msgs", "<u8"), ("reserved", "<u8")])
+assert MSG_CARRY.itemsize == 64
 RX_EVENT = np.dtype([("kind", "<u4"), ("opcode", "<u4"), ("is_ctl", "u1"), ("frame_end", "u1"),
                      ("msg_end", "u1"), ("fin", "u1"), ("code", "<u4"), ("size", "<u8"),
                      ("data_off", "<u8"), ("ctl_off", "<u8"), ("capacity", "<u8")])
@@ -101,6 +106,7 @@ SIGNATURES = [
     ("fws_gpu_unmask_gather", _I, [_P, _P, _P, _P, _U32, _P]),
     ("fws_gpu_decode_stream", _I, [_P, _P, _U64, _P, _U32, _P, _P, _P]),
     ("fws_gpu_decode_messages", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P]),
+    ("fws_gpu_decode_messages_carry", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P, _P]),
     ("fws_gpu_validate_utf8", _I, [_P, _P, _P, _U32, _P, _P]),
     ("fws_rx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_rx_session_destroy", None, [_P]),

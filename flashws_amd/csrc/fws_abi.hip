@@ -74,6 +74,9 @@ int fws_ctx_ensure_seam(fws_gpu_ctx *ctx, uint64_t span) {
 // the message planner's workspace for `frames` frames (fws_gpu_decode_messages)
 int fws_ctx_ensure_msg(fws_gpu_ctx *ctx, uint64_t frames) {
     fws_msg_ws &m = ctx->msg;
+    if (!m.cnext) {
+        if (int r = dev_alloc(&m.cnext, 1)) return r;
+    }
     if (frames <= m.cap && m.descs) return 0;
     if (frames < m.cap) frames = m.cap;
     dev_free(m.descs);
@@ -189,6 +192,7 @@ void fws_gpu_ctx_destroy(fws_gpu_ctx *ctx) {
     dev_free(ctx->msg.ctl_off);
     dev_free(ctx->msg.agg);
     dev_free(ctx->msg.pre);
+    dev_free(ctx->msg.cnext);
     delete ctx;
 }
 
@@ -379,10 +383,16 @@ int fws_gpu_decode_stream(fws_gpu_ctx *ctx, void *dev_wire, uint64_t len, fws_fr
     return fws_decode_unmask(ctx, (uint8_t *)dev_wire, len, dev_frames, cap, dev_utf8_ok, s);
 }
 
-int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len, fws_frame_info *dev_frames,
-                            uint32_t cap, fws_msg_info *dev_msgs, uint32_t msg_cap, void *dev_dst, uint64_t dst_cap,
-                            void *dev_ctl, uint64_t ctl_cap, fws_decode_result *dev_result,
-                            fws_msg_result *dev_msg_result, void *stream) {
+}  // extern "C"
+
+// fws_gpu_decode_messages (carry == null) and fws_gpu_decode_messages_carry: one
+// launch sequence; with a carry the planner starts from it, every byte / entry
+// overflow denies the gather and the control copy too, and the UTF-8 kernel --
+// always launched then, it owns *carry -- rewrites it.
+static int decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len, fws_frame_info *dev_frames,
+                           uint32_t cap, fws_msg_info *dev_msgs, uint32_t msg_cap, void *dev_dst, uint64_t dst_cap,
+                           void *dev_ctl, uint64_t ctl_cap, fws_decode_result *dev_result,
+                           fws_msg_result *dev_msg_result, fws_msg_carry *carry, void *stream) {
     if (!ctx || !dev_result || !dev_msg_result || (len && !dev_wire) || (cap && !dev_frames) ||
         (msg_cap && !dev_msgs) || (dst_cap && !dev_dst) || (ctl_cap && !dev_ctl))
         return FWS_ERR_INVALID;
@@ -418,20 +428,43 @@ int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len
     // and the gather plan take that workspace over
     const uint32_t *n_dev = ctx->dec.counters + kDecodeFramesCounter;
     if ((r = fws_launch_msg_plan(ctx, len, dev_frames, cap, n_dev, dev_result, dev_msgs, msg_cap, dst_cap, ctl_cap,
-                                 dev_msg_result, capturing, s)))
+                                 dev_msg_result, capturing, s, carry)))
         return r;
+    const fws_msg_carry_next *cn = carry ? ctx->msg.cnext : nullptr;
+    const uint32_t *deny = carry ? &ctx->msg.cnext->deny : nullptr;
     // unmask + compaction in one pass: the gather over the planner's cap descriptors
     // (the data frames' payloads with their keys, then zero-length regions)
     if (cap && dst_cap) {
         const uint64_t max_bytes = len < dst_cap ? len : dst_cap;
-        if ((r = fws_launch_gather((uint8_t *)dev_dst, wire, ctx->msg.descs, cap, ctx->plan, max_bytes, s, dst_cap)))
+        if ((r = fws_launch_gather((uint8_t *)dev_dst, wire, ctx->msg.descs, cap, ctx->plan, max_bytes, s, dst_cap,
+                                   deny)))
             return r;
     }
     if (ctl_cap && (r = fws_launch_msg_ctl(ctx, wire, dev_frames, cap, n_dev, dev_msg_result, (uint8_t *)dev_ctl,
-                                           ctl_cap, s)))
+                                           ctl_cap, s, deny)))
         return r;
-    if (cap && dst_cap) return fws_launch_utf8_msgs((const uint8_t *)dev_dst, dev_msgs, msg_cap, dev_msg_result, dst_cap, s);
+    if (carry || (cap && dst_cap))
+        return fws_launch_utf8_msgs((const uint8_t *)dev_dst, dev_msgs, msg_cap, dev_msg_result, dst_cap, s, cn, carry);
     return 0;
+}
+
+extern "C" {
+
+int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len, fws_frame_info *dev_frames,
+                            uint32_t cap, fws_msg_info *dev_msgs, uint32_t msg_cap, void *dev_dst, uint64_t dst_cap,
+                            void *dev_ctl, uint64_t ctl_cap, fws_decode_result *dev_result,
+                            fws_msg_result *dev_msg_result, void *stream) {
+    return decode_messages(ctx, dev_wire, len, dev_frames, cap, dev_msgs, msg_cap, dev_dst, dst_cap, dev_ctl, ctl_cap,
+                           dev_result, dev_msg_result, nullptr, stream);
+}
+
+int fws_gpu_decode_messages_carry(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len, fws_frame_info *dev_frames,
+                                  uint32_t cap, fws_msg_info *dev_msgs, uint32_t msg_cap, void *dev_dst,
+                                  uint64_t dst_cap, void *dev_ctl, uint64_t ctl_cap, fws_decode_result *dev_result,
+                                  fws_msg_result *dev_msg_result, fws_msg_carry *dev_carry, void *stream) {
+    if (!dev_carry) return FWS_ERR_INVALID;
+    return decode_messages(ctx, dev_wire, len, dev_frames, cap, dev_msgs, msg_cap, dev_dst, dst_cap, dev_ctl, ctl_cap,
+                           dev_result, dev_msg_result, dev_carry, stream);
 }
 
 }  // extern "C"

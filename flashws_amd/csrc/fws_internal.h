@@ -225,6 +225,17 @@ struct fws_decode_ws {
     uint32_t *bg_mark = nullptr;           // [max_nodes] k_emit: on the path
 };
 
+// fws_gpu_decode_messages_carry: what the planner hands to the call's last
+// kernel (k_utf8_msgs), which owns *dev_carry -- every planner workgroup reads
+// the carry as its initial state, so no planner thread may rewrite it, and the
+// UTF-8 fields are known only after the gather.
+struct fws_msg_carry_next {
+    fws_msg_carry next;               // the carry after this call, but for utf8_tail / utf8_bad
+    uint32_t deny;                    // 1: a byte / entry capacity was exceeded: nothing is delivered, *dev_carry stays
+    uint32_t open_cont;               // 1: the message open at the end is the one carried in
+    uint32_t old_tail, old_bad;       // utf8_tail / utf8_bad as the call found them
+};
+
 // Message-planner workspace (msg_kernels.hip), sized by the frame capacity.
 struct fws_msg_ws {
     uint64_t cap = 0;                 // frames
@@ -233,6 +244,7 @@ struct fws_msg_ws {
     uint64_t *agg = nullptr;          // [cap / 256 + 2][8] look-back words (zeroed): a workgroup's scan aggregate
     uint64_t *pre = nullptr;          // [cap / 256 + 2][8]            and its inclusive prefix
     uint32_t last_epoch = 0;          // the plan epoch of the last k_msg_plan (its tags in agg / pre)
+    fws_msg_carry_next *cnext = nullptr;   // fws_gpu_decode_messages_carry: planner -> k_utf8_msgs
 };
 
 struct fws_gpu_ctx {
@@ -293,8 +305,9 @@ int fws_launch_unmask_stream(uint8_t *base, uint64_t N, const fws_frame_info *fr
 // outplan_kernels.hip: one-launch output-space plans (base = ws.cbase, unit map, total)
 int fws_plan_next_epoch(fws_plan_ws &ws, hipStream_t s);
 // out_cap: a total above it plans nothing (*ws.total = 0: the gather writes nothing)
+// deny (optional, device word): nonzero plans nothing either
 int fws_launch_gather_plan(const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws, hipStream_t s,
-                           uint64_t out_cap = ~0ull);
+                           uint64_t out_cap = ~0ull, const uint32_t *deny = nullptr);
 int fws_launch_tx_plan(const fws_tx_desc *d, uint32_t n, fws_plan_ws &ws, uint64_t out_cap, uint64_t *out_len,
                        hipStream_t s);
 
@@ -303,21 +316,27 @@ int fws_launch_utf8_descs(const uint8_t *base, const fws_frame_desc *descs, uint
                           hipStream_t s);
 // dst_cap: regions whose total exceeds it are not gathered at all (plan + k_gather_fast only)
 int fws_launch_gather(uint8_t *dst, const uint8_t *src, const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws,
-                      uint64_t max_bytes, hipStream_t s, uint64_t dst_cap = ~0ull);
+                      uint64_t max_bytes, hipStream_t s, uint64_t dst_cap = ~0ull, const uint32_t *deny = nullptr);
 // UTF-8 verdicts of the completed TEXT entries of msgs[0, min(res->n_msgs, msg_cap)) over their
-// regions of dst (fws_gpu_decode_messages); none when res->data_bytes exceeds dst_cap
+// regions of dst (fws_gpu_decode_messages); none when res->data_bytes exceeds dst_cap.
+// carry (fws_gpu_decode_messages_carry): the verdicts take the carried left context and
+// sticky error, the open TEXT part is checked as a prefix, and *carry is rewritten from *cn
 int fws_launch_utf8_msgs(const uint8_t *dst, fws_msg_info *msgs, uint32_t msg_cap, const fws_msg_result *res,
-                         uint64_t dst_cap, hipStream_t s);
+                         uint64_t dst_cap, hipStream_t s, const fws_msg_carry_next *cn = nullptr,
+                         fws_msg_carry *carry = nullptr);
 
 // msg_kernels.hip: the message planner over the decoded frame list (n_dev frames, <= cap): the
 // compacted data-frame descriptors in ctx->msg.descs[0, cap), msgs, *out (reset: zero the look-back
-// words first, for a call whose launches are replayed); then the control payloads
+// words first, for a call whose launches are replayed); then the control payloads.
+// carry (fws_gpu_decode_messages_carry; null: the stream starts closed): the initial state,
+// read only; the planner leaves ctx->msg.cnext for fws_launch_utf8_msgs. deny: as the gather's
 int fws_launch_msg_plan(fws_gpu_ctx *ctx, uint64_t len, const fws_frame_info *frames, uint32_t cap,
                         const uint32_t *n_dev, const fws_decode_result *res, fws_msg_info *msgs, uint32_t msg_cap,
-                        uint64_t dst_cap, uint64_t ctl_cap, fws_msg_result *out, bool reset, hipStream_t s);
+                        uint64_t dst_cap, uint64_t ctl_cap, fws_msg_result *out, bool reset, hipStream_t s,
+                        const fws_msg_carry *carry = nullptr);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
-                       hipStream_t s);
+                       hipStream_t s, const uint32_t *deny = nullptr);
 
 // decode_kernels.hip
 constexpr int kDecodeFramesCounter = 3;   // index of the device frame count in dec.counters

@@ -25,6 +25,13 @@
 // cap slots -- so the gather runs over cap descriptors, a count the host knows.
 // The thread of the first error, or else of the last frame, writes the result.
 //
+// fws_gpu_decode_messages_carry (MsgPlanArgs.carry != null): the initial state
+// comes from the connection's fws_msg_carry -- closed, or open with its opcode
+// and no start frame in this call (start = kMsNoStart) -- wherever the closed
+// state stands otherwise; a truncated data frame is an absent element; the
+// result's resume_off never goes back; and the result's thread leaves the next
+// carry, but for its UTF-8 fields, in fws_msg_carry_next for k_utf8_msgs.
+//
 // k_msg_ctl: the control payloads (<= 125 B each), one wave per control frame.
 #include "fws_device.h"
 #include "fws_internal.h"
@@ -38,6 +45,7 @@ constexpr uint32_t kMsStart = 4u;       // it holds a message-start frame (start
 constexpr uint32_t kMsFirstCont = 8u;   // its first data frame is a continuation
 constexpr uint32_t kMsOpShift = 8;      // opcode of the last start frame
 constexpr uint32_t kMsOpMask = 0xFu << kMsOpShift;
+constexpr uint32_t kMsNoStart = 0xFFFFFFFFu;   // MsgScan.start: the open message began in an earlier call
 
 struct MsgScan {
     uint64_t db;        // data bytes
@@ -72,7 +80,7 @@ __device__ __forceinline__ MsgScan ms_combine(const MsgScan &L, const MsgScan &R
     o.sb = rs ? R.sb : L.sb + R.sb;
     o.sf = rs ? R.sf : L.sf + R.sf;
     o.start = rs ? R.start : L.start;
-    o.fd = ld ? L.fd : R.fd;
+    o.fd = L.fd < R.fd ? L.fd : R.fd;                  // (the initial state bears data but no frame)
     o.fl = ((rs ? R.fl : L.fl) & (kMsStart | kMsOpMask)) | ((rd ? R.fl : L.fl) & kMsOpen) |
            ((ld ? L.fl : R.fl) & kMsFirstCont) | ((L.fl | R.fl) & kMsData);
     uint32_t e = L.err < R.err ? L.err : R.err;
@@ -154,15 +162,31 @@ struct MsgPlanArgs {
     uint64_t *agg, *pre;            // look-back words, kMsSlot per workgroup
     uint32_t *ticket;
     uint32_t epoch;
+    const fws_msg_carry *carry;     // null: the stream starts closed (fws_gpu_decode_messages)
+    fws_msg_carry_next *cnext;      // with carry: the next carry, for k_utf8_msgs
 };
+
+// The state before frame 0: data-bearing and closed, or what the carry holds.
+__device__ __forceinline__ MsgScan ms_init(const MsgPlanArgs &a) {
+    MsgScan init = ms_identity();
+    init.fl = kMsData;
+    if (a.carry) {
+        // a start of its own (no bytes, no frames yet): an identity combined on its
+        // left -- the look-back's lanes past the stop -- must not take its place
+        init.fl |= kMsStart;
+        init.start = kMsNoStart;
+        const uint32_t op = a.carry->open_opcode & 0xFu;
+        if (op) init.fl |= kMsOpen | (op << kMsOpShift);
+    }
+    return init;
+}
 
 // The exclusive prefix of workgroup blk (its aggregate is `agg`), by wave 0:
 // 64 earlier workgroups per round, nearest first, up to the nearest inclusive
-// prefix; the position before workgroup 0 is the closed initial state.
+// prefix; the position before workgroup 0 is the initial state.
 __device__ __forceinline__ MsgScan ms_lookback(const MsgPlanArgs &a, uint32_t blk, const MsgScan &agg, int lane) {
     const uint64_t tag = (uint64_t)a.epoch << 48;
-    MsgScan init = ms_identity();
-    init.fl = kMsData;
+    const MsgScan init = ms_init(a);
     if (blk == 0) {
         if (lane == 0) ms_publish(a.pre, ms_combine(init, agg), tag);
         return init;
@@ -222,7 +246,8 @@ __global__ __launch_bounds__(kBlock) void k_msg_plan(MsgPlanArgs a) {
     const bool trunc = (fi.flags & FWS_FRAME_TRUNCATED) != 0 || po + fi.payload_len > a.len;
     uint64_t present = fi.payload_len;
     if (trunc) present = a.len > po ? a.len - po : 0;
-    const bool data = has && fi.opcode <= 2u, ctl = has && fi.opcode >= 8u;
+    const bool cm = a.carry != nullptr;                // whole frames only: a truncated data frame is absent
+    const bool data = has && fi.opcode <= 2u && !(cm && trunc), ctl = has && fi.opcode >= 8u;
     const bool ctl_bad = ctl && (!fi.fin || fi.payload_len > 125u);
     const bool ctl_ok = ctl && !ctl_bad && !trunc;
     const bool done = data && fi.fin && !trunc;
@@ -300,6 +325,10 @@ __global__ __launch_bounds__(kBlock) void k_msg_plan(MsgPlanArgs a) {
             m.len = (st ? 0 : ex.sb) + present;
             m.off = in.db - m.len;
             m.first_frame = st ? i : ex.start;
+            if (cm && !st && ex.start == kMsNoStart) {   // began in an earlier call: this call's part
+                m.first_frame = ex.fd != 0xFFFFFFFFu ? ex.fd : i;
+                m.flags = FWS_MSG_CONTINUED;
+            }
             m.n_data_frames = (st ? 0u : ex.sf) + 1u;
             m.opcode = st ? fi.opcode : (uint8_t)((ex.fl & kMsOpMask) >> kMsOpShift);
         }
@@ -312,11 +341,12 @@ __global__ __launch_bounds__(kBlock) void k_msg_plan(MsgPlanArgs a) {
     const bool last_ok = has && i == n - 1u && good;
     if (first_err || last_ok || (n == 0 && i64 == 0)) {
         const MsgScan &S = first_err ? ex : in;
-        const bool open = has && (S.fl & kMsOpen) != 0;
+        const bool open = (has || cm) && (S.fl & kMsOpen) != 0;
+        const bool cont = cm && open && S.start == kMsNoStart;   // the carried message is still open
         fws_msg_result r{};
         r.n_msgs = S.ne;
         r.err_frame = first_err ? i : 0xFFFFFFFFu;
-        r.open_first_frame = open ? S.start : 0xFFFFFFFFu;
+        r.open_first_frame = open ? (cont ? S.fd : S.start) : 0xFFFFFFFFu;
         r.open_opcode = open ? (S.fl & kMsOpMask) >> kMsOpShift : 0u;
         r.n_data_frames = S.nd;
         r.data_bytes = S.db;
@@ -325,11 +355,32 @@ __global__ __launch_bounds__(kBlock) void k_msg_plan(MsgPlanArgs a) {
         r.open_len = open ? S.sb : 0;
         uint64_t end = po + fi.payload_len;            // the end of the last frame processed
         if (end > a.len) end = a.len;
-        if (first_err || (ctl && trunc)) end = fi.hdr_off;
+        if (first_err || ((ctl || cm) && trunc)) end = fi.hdr_off;
         if (!has) end = 0;
-        r.resume_off = open ? a.frames[S.start].hdr_off : end;
         const int32_t parse = a.res->status;
         const bool over = S.ne > a.msg_cap || S.db > a.dst_cap || S.cb > a.ctl_cap;
+        if (cm) {
+            // parts are delivered, never resubmitted; nothing is when a byte / entry
+            // capacity was exceeded: the same bytes come again, the carry stays
+            r.resume_off = over ? 0 : end;
+            const fws_msg_carry old = *a.carry;
+            fws_msg_carry_next c{};
+            c.next.open_opcode = r.open_opcode;
+            c.next.open_frames = open ? (cont ? old.open_frames : 0u) + S.sf : 0u;
+            c.next.open_bytes = open ? (cont ? old.open_bytes : 0) + S.sb : 0;
+            c.next.prev_open_opcode = old.open_opcode;
+            c.next.prev_open_frames = old.open_frames;
+            c.next.prev_open_bytes = old.open_bytes;
+            c.next.wire_bytes = old.wire_bytes + end;
+            c.next.n_msgs = old.n_msgs + S.ne;
+            c.deny = over ? 1u : 0u;
+            c.open_cont = cont ? 1u : 0u;
+            c.old_tail = old.utf8_tail;
+            c.old_bad = old.utf8_bad;
+            *a.cnext = c;
+        } else {
+            r.resume_off = open ? a.frames[S.start].hdr_off : end;
+        }
         r.status = first_err ? (ctl_bad ? FWS_ERR_CONTROL_FRAME : FWS_ERR_SEQUENCE)
                              : (parse != 0 ? parse : (over ? FWS_ERR_CAPACITY : 0));
         *a.out = r;
@@ -343,10 +394,11 @@ __global__ __launch_bounds__(kBlock) void k_msg_ctl(const uint8_t *__restrict__ 
                                                     const uint32_t *__restrict__ n_dev, uint32_t cap,
                                                     const uint64_t *__restrict__ ctl_off,
                                                     const fws_msg_result *__restrict__ res, uint64_t ctl_cap,
-                                                    uint8_t *__restrict__ ctl) {
+                                                    uint8_t *__restrict__ ctl, const uint32_t *__restrict__ deny) {
     uint32_t n = *n_dev;
     if (n > cap) n = cap;
     if (res->ctl_bytes > ctl_cap) return;              // nothing is written when they do not fit
+    if (deny && *deny) return;                         // (the carry form: nor when anything else does not)
     const int lane = threadIdx.x & (kWave - 1);
     const uint64_t nw = (uint64_t)gridDim.x * (kBlock / kWave);
     for (uint64_t b = ((uint64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave) * kWave; b < n; b += nw * kWave) {
@@ -369,7 +421,8 @@ using namespace fwsk;
 
 int fws_launch_msg_plan(fws_gpu_ctx *ctx, uint64_t len, const fws_frame_info *frames, uint32_t cap,
                         const uint32_t *n_dev, const fws_decode_result *res, fws_msg_info *msgs, uint32_t msg_cap,
-                        uint64_t dst_cap, uint64_t ctl_cap, fws_msg_result *out, bool reset, hipStream_t s) {
+                        uint64_t dst_cap, uint64_t ctl_cap, fws_msg_result *out, bool reset, hipStream_t s,
+                        const fws_msg_carry *carry) {
     fws_plan_ws &ws = ctx->plan;
     const uint64_t nb = cap ? ((uint64_t)cap + kBlock - 1) / kBlock : 1;
     if (cap > ctx->msg.cap) return FWS_ERR_CAPACITY;
@@ -402,17 +455,19 @@ int fws_launch_msg_plan(fws_gpu_ctx *ctx, uint64_t len, const fws_frame_info *fr
     a.pre = ctx->msg.pre;
     a.ticket = ws.ticket;
     a.epoch = ws.epoch;
+    a.carry = carry;
+    a.cnext = ctx->msg.cnext;
     hipLaunchKernelGGL(k_msg_plan, dim3((unsigned)nb), dim3(kBlock), 0, s, a);
     return fws_hip_status(hipGetLastError());
 }
 
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
-                       hipStream_t s) {
+                       hipStream_t s, const uint32_t *deny) {
     if (cap == 0) return 0;
     uint64_t blocks = ((uint64_t)cap + kBlock - 1) / kBlock;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(k_msg_ctl, dim3((unsigned)blocks), dim3(kBlock), 0, s, wire, frames, n_dev, cap,
-                       ctx->msg.ctl_off, res, ctl_cap, ctl);
+                       ctx->msg.ctl_off, res, ctl_cap, ctl, deny);
     return fws_hip_status(hipGetLastError());
 }

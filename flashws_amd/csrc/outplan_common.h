@@ -19,6 +19,7 @@ struct OutPlanArgs {
     uint64_t *total;        // bytes to write (0 when they do not fit out_cap)
     uint64_t *out_len;      // TX: total, or ~0 when it exceeds out_cap; may be null
     uint64_t out_cap;
+    const uint32_t *deny;   // optional device word: nonzero = nothing fits
     uint64_t *status;
     uint32_t *ticket;
     uint32_t epoch;
@@ -63,7 +64,7 @@ __device__ __forceinline__ void out_plan_block(const Desc *__restrict__ d, uint3
             ue = (run + sz + 4095u) / 4096u;
             if (f == n - 1) {
                 const uint64_t tot = run + sz;
-                const bool fits = tot <= a.out_cap;
+                const bool fits = tot <= a.out_cap && !(a.deny && *a.deny);
                 a.base[n] = tot;
                 *a.total = fits ? tot : 0;            // nothing is written when it does not fit
                 if (a.out_len) *a.out_len = fits ? tot : ~0ull;

@@ -29,14 +29,14 @@ int fws_plan_next_epoch(fws_plan_ws &ws, hipStream_t s) {
 
 template <typename Desc>
 static int launch_out_plan(const Desc *d, uint32_t n, fws_plan_ws &ws, uint64_t out_cap, uint64_t *out_len,
-                           hipStream_t s) {
+                           hipStream_t s, const uint32_t *deny = nullptr) {
     if (n == 0) return 0;
     const bool small = n <= 16384u;                   // few frames: 64 per workgroup
     const uint32_t nb = small ? (n + 63u) / 64u : (n + kBlock - 1) / kBlock;
     if (nb > ws.status_cap) return FWS_ERR_CAPACITY;
     int r = fws_plan_next_epoch(ws, s);
     if (r) return r;
-    OutPlanArgs a{ws.cbase, ws.unit_first, ws.unit_cap, ws.total, out_len, out_cap, ws.status, ws.ticket, ws.epoch};
+    OutPlanArgs a{ws.cbase, ws.unit_first, ws.unit_cap, ws.total, out_len, out_cap, deny, ws.status, ws.ticket, ws.epoch};
     if (small)
         hipLaunchKernelGGL((k_out_plan<Desc, 64>), dim3(nb), dim3(kBlock), 0, s, d, n, a);
     else
@@ -44,8 +44,9 @@ static int launch_out_plan(const Desc *d, uint32_t n, fws_plan_ws &ws, uint64_t 
     return fws_hip_status(hipGetLastError());
 }
 
-int fws_launch_gather_plan(const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws, hipStream_t s, uint64_t out_cap) {
-    return launch_out_plan(d, n, ws, out_cap, nullptr, s);
+int fws_launch_gather_plan(const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws, hipStream_t s, uint64_t out_cap,
+                           const uint32_t *deny) {
+    return launch_out_plan(d, n, ws, out_cap, nullptr, s, deny);
 }
 
 int fws_launch_tx_plan(const fws_tx_desc *d, uint32_t n, fws_plan_ws &ws, uint64_t out_cap, uint64_t *out_len,

@@ -66,38 +66,97 @@ __global__ __launch_bounds__(kBlock) void k_utf8(const uint8_t *__restrict__ bas
     }
 }
 
+// The error flags of region [lo, hi) of k_utf8's walk, OR-ed per lane; `carry`
+// is the left context of the region's first chunk (0: none; otherwise lo is
+// 16-B aligned and it is the dword before lo). kPrefix: the region is the
+// beginning of a longer string, so only errors at byte positions inside it
+// count -- a sequence cut by hi, which fails at the zero bytes from hi on,
+// does not (utf8_err is positional).
+template <bool kPrefix>
+__device__ __forceinline__ uint32_t utf8_region_bad(uintptr_t lo, uintptr_t hi, uint32_t carry, int lane) {
+    uint32_t bad = 0;
+    for (uintptr_t w0 = lo & ~uintptr_t(15); w0 < hi + 3u; w0 += 1024u) {
+        const uintptr_t w = w0 + uintptr_t(lane) * 16u;
+        u32x4 v{0u, 0u, 0u, 0u};
+        if (w < hi) v = gload16(w);
+        const uint32_t sx = sel_bytes(w, lo, hi), sy = sel_bytes(w + 4u, lo, hi);
+        const uint32_t sz = sel_bytes(w + 8u, lo, hi), sw = sel_bytes(w + 12u, lo, hi);
+        v.x &= sx;
+        v.y &= sy;
+        v.z &= sz;
+        v.w &= sw;
+        uint32_t prev = __shfl_up(v.w, 1, 64);
+        if (lane == 0) prev = carry;
+        carry = __shfl(v.w, 63, 64);
+        if (w < hi + 3u && ((v.x | v.y | v.z | v.w | prev) & 0x80808080u)) {
+            if constexpr (kPrefix)
+                bad |= (utf8_err(v.x, prev) & sx) | (utf8_err(v.y, v.x) & sy) | (utf8_err(v.z, v.y) & sz) |
+                       (utf8_err(v.w, v.z) & sw);
+            else
+                bad |= utf8_err(v.x, prev) | utf8_err(v.y, v.x) | utf8_err(v.z, v.y) | utf8_err(v.w, v.z);
+        }
+    }
+    return bad;
+}
+
 // k_utf8 over reassembled messages (fws_gpu_decode_messages): the regions are
 // the completed TEXT entries of msgs[0, min(res->n_msgs, msg_cap)) in dst, the
 // count read on the device; the verdict goes to the entry's utf8_ok (the
 // planner preset every entry's to 0; other entries are left alone). Nothing is
 // checked when the data bytes did not fit dst (nothing was gathered).
+// kCarry (fws_gpu_decode_messages_carry): the entry that began in an earlier
+// call (FWS_MSG_CONTINUED; its part starts at dst, 16-B aligned) takes the
+// carried tail as left context and the carried error as sticky, so its verdict
+// is the whole message's. One more region, index n, is the carry's: the open
+// TEXT part at the end checked as a prefix, the new tail = the last 3 bytes of
+// (old tail, part), and *carry rewritten from *cn -- or left as found when the
+// planner denied the call (a byte / entry capacity exceeded). This kernel is
+// the call's last and the only writer of *carry; the planner copied what the
+// regions need of the old one into *cn.
+template <bool kCarry>
 __global__ __launch_bounds__(kBlock) void k_utf8_msgs(const uint8_t *__restrict__ dst, fws_msg_info *__restrict__ msgs,
                                                       uint32_t msg_cap, const fws_msg_result *__restrict__ res,
-                                                      uint64_t dst_cap) {
+                                                      uint64_t dst_cap, const fws_msg_carry_next *__restrict__ cn,
+                                                      fws_msg_carry *__restrict__ carry) {
     uint32_t n = res->n_msgs;
     if (n > msg_cap) n = msg_cap;
-    if (res->data_bytes > dst_cap) return;
+    bool skip = res->data_bytes > dst_cap;
+    if constexpr (kCarry) skip = skip || cn->deny != 0;
+    if (skip) return;
     const int lane = threadIdx.x & 63;
     const uint32_t nw = gridDim.x * (kBlock / 64);
-    for (uint32_t f = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); f < n; f += nw) {
+    const uint32_t nr = kCarry ? n + 1u : n;
+    for (uint32_t f = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); f < nr; f += nw) {
+        if constexpr (kCarry) {
+            if (f == n) {
+                fws_msg_carry c = cn->next;
+                if (c.open_opcode == 1u) {
+                    const uint64_t len = res->open_len;
+                    const uintptr_t lo = (uintptr_t)(dst + res->open_off), hi = lo + len;
+                    const uint32_t seed = cn->open_cont ? cn->old_tail : 0u;
+                    const uint32_t bad = utf8_region_bad<true>(lo, hi, seed, lane);
+                    c.utf8_bad = (__any(bad != 0) || (cn->open_cont && cn->old_bad)) ? 1u : 0u;
+                    uint32_t t = seed;
+                    for (uint64_t k = len > 3u ? len - 3u : 0; k < len; ++k)
+                        t = (t >> 8) | ((uint32_t)dst[res->open_off + k] << 24);
+                    c.utf8_tail = t & 0xFFFFFF00u;
+                }
+                if (lane == 0) *carry = c;
+                continue;
+            }
+        }
         if (msgs[f].opcode != 1u) continue;
         const uintptr_t lo = (uintptr_t)(dst + msgs[f].off), hi = lo + msgs[f].len;
-        uint32_t bad = 0, carry = 0;
-        for (uintptr_t w0 = lo & ~uintptr_t(15); w0 < hi + 3u; w0 += 1024u) {
-            const uintptr_t w = w0 + uintptr_t(lane) * 16u;
-            u32x4 v{0u, 0u, 0u, 0u};
-            if (w < hi) v = gload16(w);
-            v.x &= sel_bytes(w, lo, hi);
-            v.y &= sel_bytes(w + 4u, lo, hi);
-            v.z &= sel_bytes(w + 8u, lo, hi);
-            v.w &= sel_bytes(w + 12u, lo, hi);
-            uint32_t prev = __shfl_up(v.w, 1, 64);
-            if (lane == 0) prev = carry;
-            carry = __shfl(v.w, 63, 64);
-            if (w < hi + 3u && ((v.x | v.y | v.z | v.w | prev) & 0x80808080u))
-                bad |= utf8_err(v.x, prev) | utf8_err(v.y, v.x) | utf8_err(v.z, v.y) | utf8_err(v.w, v.z);
+        uint32_t seed = 0;
+        bool sticky = false;
+        if constexpr (kCarry) {
+            if (msgs[f].flags & FWS_MSG_CONTINUED) {
+                seed = cn->old_tail;
+                sticky = cn->old_bad != 0;
+            }
         }
-        const bool ok = !__any(bad != 0);
+        const uint32_t bad = utf8_region_bad<false>(lo, hi, seed, lane);
+        const bool ok = !__any(bad != 0) && !sticky;
         if (lane == 0) msgs[f].utf8_ok = ok ? 1 : 0;
     }
 }
@@ -637,11 +696,17 @@ int fws_launch_utf8_descs(const uint8_t *base, const fws_frame_desc *descs, uint
 }
 
 int fws_launch_utf8_msgs(const uint8_t *dst, fws_msg_info *msgs, uint32_t msg_cap, const fws_msg_result *res,
-                         uint64_t dst_cap, hipStream_t s) {
-    if (msg_cap == 0) return 0;
-    uint32_t blocks = (msg_cap + 3) / 4;
+                         uint64_t dst_cap, hipStream_t s, const fws_msg_carry_next *cn, fws_msg_carry *carry) {
+    if (msg_cap == 0 && !carry) return 0;
+    uint32_t blocks = msg_cap / 4 + 1;                   // (with a carry: one region more, never none)
+    if (!carry) blocks = (msg_cap + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_utf8_msgs, dim3(blocks), dim3(kBlock), 0, s, dst, msgs, msg_cap, res, dst_cap);
+    if (carry)
+        hipLaunchKernelGGL(k_utf8_msgs<true>, dim3(blocks), dim3(kBlock), 0, s, dst, msgs, msg_cap, res, dst_cap, cn,
+                           carry);
+    else
+        hipLaunchKernelGGL(k_utf8_msgs<false>, dim3(blocks), dim3(kBlock), 0, s, dst, msgs, msg_cap, res, dst_cap,
+                           cn, carry);
     return fws_hip_status(hipGetLastError());
 }
 
@@ -717,9 +782,9 @@ extern "C" __attribute__((visibility("default"))) uint64_t fws_internal_gather_o
 }
 
 int fws_launch_gather(uint8_t *dst, const uint8_t *src, const fws_frame_desc *d, uint32_t n, fws_plan_ws &ws,
-                      uint64_t max_bytes, hipStream_t s, uint64_t dst_cap) {
+                      uint64_t max_bytes, hipStream_t s, uint64_t dst_cap, const uint32_t *deny) {
     if (n == 0) return 0;
-    if (g_gather_one && n <= kGatherLdsMax && dst_cap == ~0ull) {
+    if (g_gather_one && n <= kGatherLdsMax && dst_cap == ~0ull && !deny) {
         uint64_t blocks = 0;
         const int r = gather_one_grid(max_bytes, &blocks);
         if (r != 0) return r;
@@ -729,7 +794,7 @@ int fws_launch_gather(uint8_t *dst, const uint8_t *src, const fws_frame_desc *d,
         if (e != hipSuccess) return fws_hip_status(e);
         return fws_hip_status(hipGetLastError());
     }
-    int r = fws_launch_gather_plan(d, n, ws, s, dst_cap);
+    int r = fws_launch_gather_plan(d, n, ws, s, dst_cap, deny);
     if (r) return r;
     uint64_t units = max_bytes / kGatherUnit + 1;
     if (units > ws.unit_cap) units = ws.unit_cap;

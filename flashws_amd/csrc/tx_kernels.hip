@@ -805,8 +805,8 @@ int fws_gpu_encode_frames(fws_gpu_ctx *ctx, void *dev_out, uint64_t out_cap, con
         const uint32_t nb = small ? (n + 63u) / 64u : (n + kBlock - 1) / kBlock;
         if (nb > ws.status_cap) return FWS_ERR_CAPACITY;
         if ((r = fws_plan_next_epoch(ws, s))) return r;
-        OutPlanArgs pa{ws.cbase, ws.unit_first, ws.unit_cap, ws.total, dev_out_len, out_cap, ws.status, ws.ticket,
-                       ws.epoch};
+        OutPlanArgs pa{ws.cbase, ws.unit_first, ws.unit_cap, ws.total, dev_out_len, out_cap, nullptr, ws.status,
+                       ws.ticket, ws.epoch};
         if (small)
             hipLaunchKernelGGL((k_tx_plan_seams<64>), dim3(nb), dim3(kBlock), 0, s, dev_descs, n, pa,
                                (const uint8_t *)dev_src, ws.tx_seam);

@@ -9,8 +9,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (DECODE_JOB, FRAME_DESC, FRAME_INFO, DECODE_RESULT, MSG_INFO, MSG_RESULT, RX_EVENT, TX_DESC,
-                   GenParams, check, lib)
+from ._lib import (DECODE_JOB, FRAME_DESC, FRAME_INFO, DECODE_RESULT, MSG_CARRY, MSG_INFO, MSG_RESULT, RX_EVENT,
+                   TX_DESC, FwsError, GenParams, check, lib)
 
 
 def _stream_handle(stream=None):
@@ -202,6 +202,122 @@ def read_msg_result(msg_result):
 def read_messages(msgs, count):
     raw = msgs[:count * MSG_INFO.itemsize].cpu().numpy()
     return np.frombuffer(raw.tobytes(), dtype=MSG_INFO).copy()
+
+
+def decode_messages_carry(ctx, wire, cap, msg_cap, dst, ctl, carry, frames=None, msgs=None, result=None,
+                          msg_result=None, stream=None, n=None, dst_cap=None, ctl_cap=None):
+    """fws_gpu_decode_messages_carry: decode_messages for one read of a
+    connection. carry is the connection's fws_msg_carry, a 64-byte device uint8
+    tensor (zeros for a new connection) that the call reads and rewrites on the
+    stream; wire holds the bytes from the previous call's resume_off on.
+    Returns (status, frames, msgs, result, msg_result) -- device tensors,
+    nothing synchronised."""
+    dev = wire.device
+    if frames is None:
+        frames = torch.empty(max(cap, 1) * FRAME_INFO.itemsize, dtype=torch.uint8, device=dev)
+    if msgs is None:
+        msgs = torch.empty(max(msg_cap, 1) * MSG_INFO.itemsize, dtype=torch.uint8, device=dev)
+    if result is None:
+        result = torch.empty(DECODE_RESULT.itemsize, dtype=torch.uint8, device=dev)
+    if msg_result is None:
+        msg_result = torch.empty(MSG_RESULT.itemsize, dtype=torch.uint8, device=dev)
+    n = wire.numel() if n is None else n
+    dst_cap = dst.numel() if dst_cap is None else dst_cap
+    ctl_cap = ctl.numel() if ctl_cap is None else ctl_cap
+    rc = lib().fws_gpu_decode_messages_carry(ctx.h, _ptr(wire), n, _ptr(frames), cap, _ptr(msgs), msg_cap,
+                                             _ptr(dst), dst_cap, _ptr(ctl), ctl_cap, _ptr(result),
+                                             _ptr(msg_result), _ptr(carry), _stream_handle(stream))
+    return rc, frames, msgs, result, msg_result
+
+
+def read_msg_carry(carry):
+    return np.frombuffer(carry.cpu().numpy().tobytes(), dtype=MSG_CARRY)[0]
+
+
+class MessageStream:
+    """One connection's reads turned into its messages and control frames: the
+    caller's side of fws_gpu_decode_messages_carry in its reference form.
+
+    feed(data) puts the bytes the previous call left (from its resume_off on:
+    an unfinished frame) in front of data, makes one carry call and one
+    synchronisation, and returns the units that call completed, in order, as
+    (opcode, bytes, utf8_ok) -- utf8_ok is the verdict of a TEXT message, False
+    otherwise. A message that arrives over several reads is delivered once,
+    at its FIN frame, its parts joined; the parts are kept on the host, the
+    wire bytes of a finished frame are never kept. max_read bounds one feed,
+    max_frame a frame's header and payload (a frame must fit in the buffer).
+    The buffers are sized so that no capacity can be exceeded. A protocol or
+    sequencing error is left in `status`; the units before it are returned and
+    a later feed raises."""
+
+    def __init__(self, ctx, max_read, max_frame=1 << 16, device="cuda:0"):
+        self.ctx = ctx
+        self.max_read = max_read
+        self.wire_cap = (max_read + max_frame + 15) & ~15
+        self.cap = self.wire_cap // 6 + 1            # a client frame is at least 6 bytes
+        dev = torch.device(device)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        self.wire = torch.zeros(self.wire_cap, **u8)
+        self.dst = torch.zeros(self.wire_cap, **u8)
+        self.ctl = torch.zeros(self.wire_cap, **u8)
+        self.frames = torch.zeros(self.cap * FRAME_INFO.itemsize, **u8)
+        self.msgs = torch.zeros(self.cap * MSG_INFO.itemsize, **u8)
+        self.result = torch.zeros(DECODE_RESULT.itemsize, **u8)
+        self.msg_result = torch.zeros(MSG_RESULT.itemsize, **u8)
+        self.carry = torch.zeros(MSG_CARRY.itemsize, **u8)
+        pin = dict(dtype=torch.uint8, pin_memory=True)
+        self._h_wire = torch.zeros(self.wire_cap, **pin)
+        self._h_dst = torch.zeros(self.wire_cap, **pin)
+        self._h_ctl = torch.zeros(self.wire_cap, **pin)
+        self._h_msgs = torch.zeros(self.cap * MSG_INFO.itemsize, **pin)
+        self._h_res = torch.zeros(MSG_RESULT.itemsize, **pin)
+        self._pending = b""
+        self._parts = []
+        self.status = 0
+
+    def feed(self, data):
+        if self.status not in (0, _lib.FWS_ERR_CAPACITY):
+            raise FwsError("MessageStream.feed after an error", self.status)
+        data = bytes(data)
+        if len(data) > self.max_read:
+            raise ValueError(f"a read of {len(data)} bytes exceeds max_read = {self.max_read}")
+        buf = self._pending + data
+        n = len(buf)
+        if n > self.wire_cap:
+            raise ValueError("a frame exceeds max_frame: the unfinished frame and the read do not fit the buffer")
+        ne = n // 6 + 1
+        stream = torch.cuda.current_stream(self.wire.device)
+        self._h_wire[:n] = torch.frombuffer(bytearray(buf), dtype=torch.uint8) if n else self._h_wire[:0]
+        self.wire[:n].copy_(self._h_wire[:n], non_blocking=True)
+        rc, *_ = decode_messages_carry(self.ctx, self.wire, self.cap, self.cap, self.dst, self.ctl, self.carry,
+                                       frames=self.frames, msgs=self.msgs, result=self.result,
+                                       msg_result=self.msg_result, stream=stream, n=n)
+        check("fws_gpu_decode_messages_carry", rc)
+        self._h_res.copy_(self.msg_result, non_blocking=True)
+        self._h_msgs[:ne * MSG_INFO.itemsize].copy_(self.msgs[:ne * MSG_INFO.itemsize], non_blocking=True)
+        self._h_dst[:n].copy_(self.dst[:n], non_blocking=True)
+        self._h_ctl[:n].copy_(self.ctl[:n], non_blocking=True)
+        stream.synchronize()
+        r = np.frombuffer(self._h_res.numpy().tobytes(), dtype=MSG_RESULT)[0]
+        entries = np.frombuffer(self._h_msgs.numpy()[:int(r["n_msgs"]) * MSG_INFO.itemsize].tobytes(), dtype=MSG_INFO)
+        dst, ctl = self._h_dst.numpy(), self._h_ctl.numpy()
+        units = []
+        for e in entries:
+            off, ln = int(e["off"]), int(e["len"])
+            if e["opcode"] >= 8:
+                units.append((int(e["opcode"]), ctl[off:off + ln].tobytes(), False))
+                continue
+            body = dst[off:off + ln].tobytes()
+            if e["flags"] & _lib.FWS_MSG_CONTINUED:
+                body = b"".join(self._parts) + body
+            self._parts = []
+            units.append((int(e["opcode"]), body, bool(e["utf8_ok"])))
+        if int(r["open_opcode"]) and int(r["open_len"]):
+            off = int(r["open_off"])
+            self._parts.append(dst[off:off + int(r["open_len"])].tobytes())
+        self._pending = buf[int(r["resume_off"]):]
+        self.status = int(r["status"])
+        return units
 
 
 class DecodeEngine:

@@ -211,9 +211,9 @@ typedef struct fws_msg_info {
     uint32_t n_data_frames; /* fragments of the message (control: 1) */
     uint8_t opcode;         /* 1 TEXT, 2 BIN, 8 CLOSE, 9 PING, 10 PONG */
     uint8_t utf8_ok;        /* TEXT message: 1 iff the reassembled bytes are well-formed UTF-8; else 0 */
-    uint8_t flags;          /* 0 */
+    uint8_t flags;          /* 0; fws_gpu_decode_messages_carry: FWS_MSG_CONTINUED */
     uint8_t pad;
-} fws_msg_info;             /* 32 bytes */
+} fws_msg_info;            /* 32 bytes */
 
 typedef struct fws_msg_result {
     int32_t status;         /* see fws_gpu_decode_messages */
@@ -265,9 +265,11 @@ typedef struct fws_msg_result {
  *   3. else FWS_ERR_CAPACITY when n_frames > cap, n_msgs > msg_cap or a byte
  *      capacity was exceeded;
  *   4. else 0.
- * Out of scope: carrying an open message and its UTF-8 state across calls,
- * UTF-8 validation of CLOSE reasons, client-side streams, the C++ adapter and
- * the FLoop hook. */
+ * Every call starts from "no message open"; a connection whose bytes arrive in
+ * reads uses fws_gpu_decode_messages_carry below, which carries the open
+ * message and its UTF-8 state from call to call.
+ * Out of scope: UTF-8 validation of CLOSE reasons, client-side streams, the C++
+ * adapter and the FLoop hook. */
 int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len,
                             fws_frame_info *dev_frames, uint32_t cap,
                             fws_msg_info *dev_msgs, uint32_t msg_cap,
@@ -275,6 +277,85 @@ int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len
                             void *dev_ctl, uint64_t ctl_cap,
                             fws_decode_result *dev_result, fws_msg_result *dev_msg_result,
                             void *stream);
+
+/* ---- the same for a connection read by read --------------------------------
+ * A connection delivers its bytes in reads; OnRecvData hands out a message's
+ * parts as they arrive and carries a few words of state between reads
+ * (w_socket.h:223-245, 713-747). fws_msg_carry is that state for
+ * fws_gpu_decode_messages_carry, in device memory: the call's kernels read it
+ * and rewrite it, so two calls queued on one stream chain through it without
+ * the host. */
+#define FWS_MSG_CONTINUED 1u     /* fws_msg_info.flags: the message began in an earlier call */
+
+typedef struct fws_msg_carry {   /* device memory; all zero = a new connection */
+    uint32_t open_opcode;        /* 0: no message open; 1 TEXT / 2 BIN */
+    uint32_t open_frames;        /* data frames of the open message delivered so far (all calls) */
+    uint64_t open_bytes;         /* its bytes delivered so far (all calls) */
+    uint32_t utf8_tail;          /* open TEXT message: its last 3 delivered bytes, placed as the
+                                    "previous dword" of the UTF-8 check (bits 31:24 the last byte,
+                                    bits 7:0 zero; zeros where fewer than 3 exist) */
+    uint32_t utf8_bad;           /* 1: the open TEXT message is already malformed (RFC 6455 §8.1
+                                    allows failing early) */
+    uint32_t prev_open_opcode;   /* open_opcode / open_frames / open_bytes as the last call found them: */
+    uint32_t prev_open_frames;   /*   what a FWS_MSG_CONTINUED entry's len / n_data_frames add to */
+    uint64_t prev_open_bytes;
+    uint64_t wire_bytes;         /* running sum of resume_off over the calls */
+    uint64_t n_msgs;             /* running count of entries delivered */
+    uint64_t reserved;           /* 0 */
+} fws_msg_carry;            /* 64 bytes */
+
+/* fws_gpu_decode_messages for one read of a connection: dev_wire[0..len) is
+ * the bytes from the previous call's resume_off on (what was left, then the
+ * new read), starting at a frame header. *dev_carry is the connection's state
+ * (NULL: FWS_ERR_INVALID). Stream-ordered like everything else here: no host
+ * synchronisation, no device-to-host copy, no allocation after
+ * fws_gpu_ctx_reserve. What is not listed is fws_gpu_decode_messages' contract
+ * unchanged (the parse, dev_frames / *dev_result, the control frames' packing,
+ * the status order, the alignment rules, dev_wire never written).
+ *   initial state  the planner starts from the carry. With a message open a
+ *             leading TEXT / BIN frame is FWS_ERR_SEQUENCE at that frame and a
+ *             leading continuation is legal; with none open the other way round.
+ *   whole frames   a truncated last frame, data or control, contributes
+ *             nothing: it is not gathered, counted or sequence-checked, and
+ *             resume_off is its hdr_off. Otherwise resume_off is the end of the
+ *             last frame processed, or the failing header on a sequencing error.
+ *             It never goes back to a message's first header. A frame must fit
+ *             in the buffer the caller resubmits.
+ *   parts     dev_dst holds this call's data bytes in wire order. A message
+ *             completed here that began in an earlier call gets one entry with
+ *             flags = FWS_MSG_CONTINUED whose off (always 0) / len /
+ *             n_data_frames describe this call's part and whose first_frame is
+ *             its first data frame of this call; the message's totals are
+ *             prev_open_bytes + len and prev_open_frames + n_data_frames. The
+ *             present bytes of a message still open at the end are a part too
+ *             (open_off / open_len) and are never resubmitted. open_opcode != 0
+ *             is the "open" test; open_first_frame is the message's first data
+ *             frame in this call, 0xFFFFFFFF if it has none here.
+ *   UTF-8     a TEXT entry's utf8_ok is the verdict on the whole message,
+ *             earlier parts included: the call's first region takes utf8_tail
+ *             as its left context and utf8_bad is sticky. The open TEXT part at
+ *             the end is checked as a prefix (a sequence cut by its end is no
+ *             error yet). An invalid byte (C0, C1, F5..FF) is flagged at the byte
+ *             after it, so as a part's last byte it sets utf8_bad one call
+ *             later; the final verdict is exact.
+ *   errors    on a sequencing error at frame e the carry, like the open-message
+ *             fields, describes the state just before e.
+ *   capacity  n_frames > cap: FWS_ERR_CAPACITY, but the first cap frames are
+ *             processed and the carry and resume_off are valid -- the caller
+ *             continues from resume_off. data_bytes > dst_cap, ctl_bytes >
+ *             ctl_cap or n_msgs > msg_cap: nothing is written to dev_dst or
+ *             dev_ctl, *dev_carry is left exactly as found and resume_off = 0
+ *             (the counts are still reported): the caller retries the same
+ *             bytes with larger buffers.
+ * Out of scope: resuming inside a frame's payload, UTF-8 validation of CLOSE
+ * reasons, client-side streams, the C++ adapter and the FLoop hook. */
+int fws_gpu_decode_messages_carry(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len,
+                                  fws_frame_info *dev_frames, uint32_t cap,
+                                  fws_msg_info *dev_msgs, uint32_t msg_cap,
+                                  void *dev_dst, uint64_t dst_cap,
+                                  void *dev_ctl, uint64_t ctl_cap,
+                                  fws_decode_result *dev_result, fws_msg_result *dev_msg_result,
+                                  fws_msg_carry *dev_carry, void *stream);
 
 /* ---- batched stream decode: many independent streams ----------------------
  * fws_gpu_decode_stream over a list of independent streams (the buffers of

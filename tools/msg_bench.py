@@ -12,7 +12,24 @@ Per workload, microseconds per call (median of the rounds):
   gather     fws_gpu_unmask_gather over the data frames' descriptors
   utf8       fws_gpu_validate_utf8 over the reassembled messages in dst
 and messages / (parse + gather + utf8). One JSON line per workload.
-usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out FILE]"""
+
+--carry measures fws_gpu_decode_messages_carry instead:
+  (i)  carry_cost   workload (b) whole in one call: the carry form and this
+       tree's fws_gpu_decode_messages against the same call of a library built
+       from the parent commit (--parent-lib), two contexts of which give the
+       A/A spread; the forms alternate within every round.
+  (ii) carry_reads  the stream cut into --read-mib reads at arbitrary byte
+       offsets, decoded by the carry protocol (each call from the last
+       resume_off: the unfinished frame) and by the resubmit protocol of the
+       old call (from the open message's first header), each call's bytes
+       first copied to a 16-B aligned buffer, as a caller must. Total device
+       time per pass of the whole stream and the bytes each protocol parsed;
+       for workload (b) and for one BIN message of the same size in 64 KiB
+       fragments (BASELINE config 4's shape). The buffers of both protocols are
+       worked out on the host from the frame list and checked against every
+       call's resume_off in an untimed pass first.
+usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out FILE]
+       python tools/msg_bench.py --carry [--parent-lib SO] [--read-mib M] [--target MiB] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -79,6 +96,197 @@ def fragmented_stream(target, seed=42):
     regions["payload_off"] = [m[0] for m in msgs]
     regions["payload_len"] = [m[1] for m in msgs]
     return wire, descs, regions, len(frames)
+
+
+def one_message_stream(target, frag=65536, seed=7):
+    """One BIN message of `target` bytes in `frag`-byte fragments (BASELINE config 4's shape)."""
+    rng = np.random.default_rng(seed)
+    n = target // frag
+    hdr = len(header(0, 0, frag, 0))
+    wire = rng.integers(0, 256, n * (hdr + frag), dtype=np.uint8)
+    for j in range(n):
+        h = header(2 if j == 0 else 0, int(j == n - 1), frag, int(rng.integers(0, 1 << 32)))
+        wire[j * (hdr + frag):j * (hdr + frag) + hdr] = np.frombuffer(h, dtype=np.uint8)
+    return wire
+
+
+def walk(wire):
+    """The frame list of a well-formed stream: per frame (hdr_off, end, the first
+    header of its message -- its own for a control frame --, whether a message is
+    open after it and that message's first header)."""
+    out, pos, n, msg0, is_open = [], 0, len(wire), 0, False
+    while pos < n:
+        b0, l7 = int(wire[pos]), int(wire[pos + 1]) & 127
+        h, ln = 6, l7
+        if l7 == 126:
+            h, ln = 8, int.from_bytes(wire[pos + 2:pos + 4].tobytes(), "big")
+        elif l7 == 127:
+            h, ln = 14, int.from_bytes(wire[pos + 2:pos + 10].tobytes(), "big")
+        op = b0 & 15
+        if op in (1, 2):
+            msg0 = pos
+        if op < 8:
+            is_open = not b0 >> 7
+        out.append((pos, pos + h + ln, msg0 if op < 8 else pos, is_open, msg0))
+        pos += h + ln
+    return out
+
+
+def read_buffers(wire, cuts):
+    """Per protocol, the (start, end) of every call's bytes when the stream arrives cut at `cuts`."""
+    fr = walk(wire)
+    starts = np.array([f[0] for f in fr])
+    carry, old, a, b = [], [], 0, 0
+    for c in list(cuts) + [len(wire)]:
+        carry.append((a, c))
+        old.append((b, c))
+        k = int(np.searchsorted(starts, c, side="right")) - 1    # the frame holding byte c - 0 (c > 0)
+        hdr_off, end, m0, is_open, open0 = fr[k]
+        if c >= end:                                  # on a frame boundary: nothing left of frame k
+            a, b = c, (open0 if is_open else c)
+        elif c - hdr_off < (6 if end - hdr_off < 132 else 8 if end - hdr_off < 65550 else 14):
+            # inside frame k's header: the parse stops before it, the state is frame k - 1's
+            a = hdr_off
+            b = fr[k - 1][4] if k and fr[k - 1][3] else hdr_off
+        else:                                         # inside its payload
+            a = hdr_off
+            open_before = k and fr[k - 1][3]
+            b = m0 if (wire[hdr_off] & 15) < 8 else (fr[k - 1][4] if open_before else hdr_off)
+    return carry, old
+
+
+def carry_cost(wire, n_frames, parent_lib, rounds, steps):
+    dev = torch.device("cuda:0")
+    cap = n_frames + 64
+    P = C.CDLL(parent_lib)
+    for name, res, args in _lib.SIGNATURES:
+        if hasattr(P, name):
+            getattr(P, name).restype, getattr(P, name).argtypes = res, args
+    assert not hasattr(P, "fws_gpu_decode_messages_carry"), "--parent-lib is this tree's library"
+    srcs = [torch.from_numpy(wire).to(dev) for _ in range(4)]
+    dsts = [torch.empty(len(wire), dtype=torch.uint8, device=dev) for _ in range(4)]
+    ctl = torch.empty(1 << 20, dtype=torch.uint8, device=dev)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    frames, msgs = torch.empty(cap * 24, **u8), torch.empty(cap * 32, **u8)
+    res, mres, carry = torch.empty(40, **u8), torch.empty(64, **u8), torch.zeros(64, **u8)
+    s = torch.cuda.current_stream()
+    ctx = gpu.Ctx(0, max_frames=cap, max_stream_bytes=len(wire))
+    pctx = []
+    for _ in range(2):
+        h = C.c_void_p()
+        assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0 and P.fws_gpu_ctx_reserve(h, cap, len(wire)) == 0
+        pctx.append(h)
+
+    def parent(h):
+        def f(i):
+            assert P.fws_gpu_decode_messages(h, srcs[i % 4].data_ptr(), len(wire), frames.data_ptr(), cap,
+                                             msgs.data_ptr(), cap, dsts[i % 4].data_ptr(), len(wire), ctl.data_ptr(),
+                                             1 << 20, res.data_ptr(), mres.data_ptr(), s.cuda_stream) == 0
+        return f
+
+    def f_new_old(i):
+        assert gpu.decode_messages(ctx, srcs[i % 4], cap, cap, dsts[i % 4], ctl, frames=frames, msgs=msgs, result=res,
+                                   msg_result=mres)[0] == 0
+
+    def f_carry(i):
+        assert gpu.decode_messages_carry(ctx, srcs[i % 4], cap, cap, dsts[i % 4], ctl, carry, frames=frames,
+                                         msgs=msgs, result=res, msg_result=mres)[0] == 0
+
+    forms = {"parent_a": parent(pctx[0]), "parent_b": parent(pctx[1]), "messages": f_new_old, "carry": f_carry}
+    want = None
+    for k, f in forms.items():                        # the same result from every form
+        f(0)
+        r = gpu.read_msg_result(mres)
+        got = (int(r["status"]), int(r["n_msgs"]), int(r["data_bytes"]), dsts[0][:1 << 20].cpu().numpy().tobytes())
+        want = want or got
+        assert got == want and got[0] == 0, k
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(timed(forms[k], steps))
+    out = {"measure": "carry_cost", "workload": "frag", "wire_bytes": len(wire), "frames": n_frames,
+           "messages": want[1], "rounds": rounds, "steps": steps, "device": torch.cuda.get_device_name(0),
+           "parent_lib": os.path.basename(parent_lib)}
+    for k in forms:
+        out[k + "_us"] = round(statistics.median(times[k]), 2)
+        out[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    out["aa_spread_us"] = round(abs(out["parent_a_us"] - out["parent_b_us"]), 2)
+    out["carry_minus_parent_us"] = round(out["carry_us"] - min(out["parent_a_us"], out["parent_b_us"]), 2)
+    for h in pctx:
+        P.fws_gpu_ctx_destroy(h)
+    ctx.close()
+    return out
+
+
+def carry_reads(name, wire, read_bytes, rounds, seed=11):
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(seed)
+    n = len(wire)
+    cuts = sorted(set(int(c) + int(rng.integers(-4096, 4096)) for c in range(read_bytes, n, read_bytes)))
+    bufs = dict(zip(("carry", "resubmit"), read_buffers(wire, cuts)))
+    fr = walk(wire)
+    ends = np.array([f[1] for f in fr])
+    starts = np.array([f[0] for f in fr])
+    src = torch.from_numpy(wire).to(dev)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    out = {"measure": "carry_reads", "workload": name, "wire_bytes": n, "frames": len(fr), "read_bytes": read_bytes,
+           "calls": len(cuts) + 1, "rounds": rounds, "device": torch.cuda.get_device_name(0)}
+    run = {}
+    for proto, bl in bufs.items():
+        longest = max(b - a for a, b in bl)
+        cap = max(int(np.searchsorted(starts, b) - np.searchsorted(starts, a)) for a, b in bl) + 64
+        ctx = gpu.Ctx(0, max_frames=cap, max_stream_bytes=longest)
+        buf, dst = torch.empty(longest + 16, **u8), torch.empty(longest + 16, **u8)
+        ctl = torch.empty(1 << 20, **u8)
+        frames, msgs = torch.empty(cap * 24, **u8), torch.empty(cap * 32, **u8)
+        res, mres, carry = torch.empty(40, **u8), torch.empty(64, **u8), torch.zeros(64, **u8)
+
+        def one(a, b, proto=proto, ctx=ctx, buf=buf, dst=dst, ctl=ctl, frames=frames, msgs=msgs, res=res, mres=mres,
+                carry=carry, cap=cap):
+            buf[:b - a].copy_(src[a:b])               # the caller's move to an aligned buffer
+            if proto == "carry":
+                rc = gpu.decode_messages_carry(ctx, buf, cap, cap, dst, ctl, carry, frames=frames, msgs=msgs,
+                                               result=res, msg_result=mres, n=b - a)[0]
+            else:
+                rc = gpu.decode_messages(ctx, buf, cap, cap, dst, ctl, frames=frames, msgs=msgs, result=res,
+                                         msg_result=mres, n=b - a)[0]
+            assert rc == 0
+
+        # untimed, checked: every call resumes where the host walk says, every unit is delivered
+        delivered = 0
+        for j, (a, b) in enumerate(bl):
+            one(a, b)
+            r = gpu.read_msg_result(mres)
+            nxt = bl[j + 1][0] if j + 1 < len(bl) else n
+            assert int(r["status"]) == 0 and a + int(r["resume_off"]) == nxt, (proto, j, a, int(r["resume_off"]), nxt)
+            delivered += int(r["n_msgs"])
+        if proto == "carry":
+            c = gpu.read_msg_carry(carry)
+            assert int(c["wire_bytes"]) == n and int(c["n_msgs"]) == delivered and int(c["open_opcode"]) == 0
+        out[proto + "_entries"] = delivered
+        out[proto + "_bytes_parsed"] = int(sum(b - a for a, b in bl))
+        out[proto + "_longest_call_bytes"] = int(longest)
+        run[proto] = (one, bl, carry, ctx)
+    times = {k: [] for k in run}
+    for rnd in range(rounds + 1):                     # (round 0 warms up)
+        for proto in (list(run) if rnd % 2 == 0 else list(run)[::-1]):
+            one, bl, carry, _ = run[proto]
+            carry.zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for a, b in bl:
+                one(a, b)
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd:
+                times[proto].append(e0.elapsed_time(e1) * 1e3)
+    for proto in run:
+        out[proto + "_total_us"] = round(statistics.median(times[proto]), 1)
+        out[proto + "_total_us_min_max"] = [round(min(times[proto]), 1), round(max(times[proto]), 1)]
+        run[proto][3].close()
+    out["resubmit_over_carry"] = round(out["resubmit_total_us"] / out["carry_total_us"], 3)
+    return out
 
 
 def c3_stream(target):
@@ -176,9 +384,24 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--only", default="", help="c3 or frag")
     ap.add_argument("--out", default="")
+    ap.add_argument("--carry", action="store_true", help="measure fws_gpu_decode_messages_carry (see above)")
+    ap.add_argument("--parent-lib", default="", help="libfws_gpu.so built from the parent commit, for (i)")
+    ap.add_argument("--read-mib", type=float, default=2.0)
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.carry:
+        wire, _, _, n_frames = fragmented_stream(target)
+        if a.parent_lib:
+            lines.append(json.dumps(carry_cost(wire, n_frames, os.path.abspath(a.parent_lib), a.rounds, a.steps)))
+            print(lines[-1], flush=True)
+        for name, w in (("frag", wire), ("one_message_64k", one_message_stream(target))):
+            lines.append(json.dumps(carry_reads(name, w, int(a.read_mib * (1 << 20)), a.rounds)))
+            print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     for name, make in (("c3", c3_stream), ("frag", fragmented_stream)):
         if a.only and a.only != name:
             continue
