@@ -35,6 +35,7 @@ FWS_ERR_CAPACITY = -20
 FWS_ERR_INVALID = -21
 FWS_ERR_NO_DEVICE = -22
 FWS_ERR_INTERNAL = -23
+FWS_ERR_DECLINED = -24
 FWS_ERR_HIP_BASE = -1000
 
 # include/fws_gpu.h structs as numpy dtypes (device arrays are torch uint8 views)
@@ -56,6 +57,13 @@ MSG_CARRY = np.dtype([("open_opcode", "<u4"), ("open_frames", "<u4"), ("open_byt
                       ("utf8_bad", "<u4"), ("prev_open_opcode", "<u4"), ("prev_open_frames", "<u4"),
                       ("prev_open_bytes", "<u8"), ("wire_bytes", "<u8"), ("n_msgs", "<u8"), ("reserved", "<u8")])
 assert MSG_CARRY.itemsize == 64
+# fws_gpu_decode_messages_multi: a read's limits and its descriptor
+FWS_MSG_MULTI_MAX_READ = 128 << 10
+FWS_MSG_MULTI_MAX_FRAMES = 256
+MSG_READ = np.dtype([("wire_off", "<u8"), ("dst_off", "<u8"), ("ctl_off", "<u8"), ("len", "<u4"), ("conn", "<u4"),
+                     ("dst_cap", "<u4"), ("ctl_cap", "<u4"), ("frame_base", "<u4"), ("frame_cap", "<u4"),
+                     ("msg_base", "<u4"), ("msg_cap", "<u4"), ("reserved", "<u8")])
+assert MSG_READ.itemsize == 64
 RX_EVENT = np.dtype([("kind", "<u4"), ("opcode", "<u4"), ("is_ctl", "u1"), ("frame_end", "u1"),
                      ("msg_end", "u1"), ("fin", "u1"), ("code", "<u4"), ("size", "<u8"),
                      ("data_off", "<u8"), ("ctl_off", "<u8"), ("capacity", "<u8")])
@@ -107,6 +115,7 @@ SIGNATURES = [
     ("fws_gpu_decode_stream", _I, [_P, _P, _U64, _P, _U32, _P, _P, _P]),
     ("fws_gpu_decode_messages", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P]),
     ("fws_gpu_decode_messages_carry", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P, _P]),
+    ("fws_gpu_decode_messages_multi", _I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P]),
     ("fws_gpu_validate_utf8", _I, [_P, _P, _P, _U32, _P, _P]),
     ("fws_rx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_rx_session_destroy", None, [_P]),

@@ -334,6 +334,11 @@ int fws_launch_msg_plan(fws_gpu_ctx *ctx, uint64_t len, const fws_frame_info *fr
                         const uint32_t *n_dev, const fws_decode_result *res, fws_msg_info *msgs, uint32_t msg_cap,
                         uint64_t dst_cap, uint64_t ctl_cap, fws_msg_result *out, bool reset, hipStream_t s,
                         const fws_msg_carry *carry = nullptr);
+// fws_gpu_decode_messages_multi (msg_multi_kernels.hip): n reads, one workgroup each; no workspace
+int fws_launch_msg_multi(const uint8_t *wire, const fws_msg_read *reads, uint32_t n, uint32_t max_len,
+                         fws_frame_info *frames, fws_msg_info *msgs, uint8_t *dst, uint8_t *ctl,
+                         fws_decode_result *res, fws_msg_result *mres, fws_msg_carry *carries, uint32_t n_conns,
+                         hipStream_t s);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
                        hipStream_t s, const uint32_t *deny = nullptr);

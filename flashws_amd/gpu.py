@@ -9,8 +9,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (DECODE_JOB, FRAME_DESC, FRAME_INFO, DECODE_RESULT, MSG_CARRY, MSG_INFO, MSG_RESULT, RX_EVENT,
-                   TX_DESC, FwsError, GenParams, check, lib)
+from ._lib import (DECODE_JOB, FRAME_DESC, FRAME_INFO, DECODE_RESULT, MSG_CARRY, MSG_INFO, MSG_READ, MSG_RESULT,
+                   RX_EVENT, TX_DESC, FwsError, GenParams, check, lib)
 
 
 def _stream_handle(stream=None):
@@ -318,6 +318,129 @@ class MessageStream:
         self._pending = buf[int(r["resume_off"]):]
         self.status = int(r["status"])
         return units
+
+
+def decode_messages_multi(ctx, wire, reads, n, max_len, frames, msgs, dst, ctl, results, msg_results, carries,
+                          n_conns, stream=None):
+    """fws_gpu_decode_messages_multi: the reads of many connections in one
+    launch. reads holds n fws_msg_read descriptors (_lib.MSG_READ) in a device
+    uint8 tensor; every other argument is the device uint8 tensor the
+    descriptors' offsets and slices refer to, results / msg_results n records
+    each, carries n_conns fws_msg_carry records. Returns the call's status --
+    per-read outcomes are in msg_results; nothing is synchronised."""
+    return lib().fws_gpu_decode_messages_multi(ctx.h, _ptr(wire), _ptr(reads), n, max_len, _ptr(frames), _ptr(msgs),
+                                               _ptr(dst), _ptr(ctl), _ptr(results), _ptr(msg_results),
+                                               _ptr(carries), n_conns, _stream_handle(stream))
+
+
+class MessageMux:
+    """MessageStream for many connections: feed({conn: bytes, ...}) makes one
+    fws_gpu_decode_messages_multi call and one synchronisation for all of them
+    and returns {conn: [(opcode, bytes, utf8_ok), ...]}, the units each
+    connection completed, in order. Per connection the host protocol is
+    MessageStream's: the bytes from resume_off on are kept in front of the next
+    read, the parts of a message that arrives over several reads are joined at
+    its FWS_MSG_CONTINUED entry. A read the one-launch form declines (over
+    _lib.FWS_MSG_MULTI_MAX_FRAMES headers) goes through decode_messages_carry
+    with that connection's carry. A connection whose status is a protocol or
+    sequencing error keeps it in status[conn]; feeding it again raises, the
+    others go on. max_read bounds one connection's feed, max_frame a frame."""
+
+    def __init__(self, ctx, n_conns, max_read, max_frame=1 << 16, device="cuda:0"):
+        self.ctx, self.n_conns, self.max_read = ctx, n_conns, max_read
+        self.slot = (max_read + max_frame + 15) & ~15
+        if self.slot > _lib.FWS_MSG_MULTI_MAX_READ:
+            raise ValueError("max_read + max_frame exceeds FWS_MSG_MULTI_MAX_READ")
+        self.cap = min(self.slot // 6 + 1, _lib.FWS_MSG_MULTI_MAX_FRAMES)
+        self.dev = torch.device(device)
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        pin = dict(dtype=torch.uint8, pin_memory=True)
+        self._sizes = dict(wire=self.slot, dst=self.slot, ctl=self.slot, frames=self.cap * FRAME_INFO.itemsize,
+                           msgs=self.cap * MSG_INFO.itemsize, res=DECODE_RESULT.itemsize, mres=MSG_RESULT.itemsize,
+                           reads=MSG_READ.itemsize)
+        self._d = {k: torch.zeros(n_conns * sz, **u8) for k, sz in self._sizes.items()}
+        self._h = {k: torch.zeros(n_conns * sz, **pin) for k, sz in self._sizes.items()}
+        self.carries = torch.zeros(n_conns * MSG_CARRY.itemsize, **u8)
+        self._single = None
+        self._pending = [b""] * n_conns
+        self._parts = [[] for _ in range(n_conns)]
+        self.status = [0] * n_conns
+
+    def _fallback(self, conn, buf):
+        """A declined read: the carry call on the same bytes with the connection's carry."""
+        if self._single is None:
+            self._single = MessageStream(self.ctx, self.max_read, self.slot - self.max_read - 15, device=self.dev)
+        ms = self._single
+        csz = MSG_CARRY.itemsize
+        ms.carry.copy_(self.carries[conn * csz:(conn + 1) * csz])
+        ms._pending, ms._parts, ms.status = buf, self._parts[conn], 0
+        units = ms.feed(b"")
+        self.carries[conn * csz:(conn + 1) * csz].copy_(ms.carry)
+        self._pending[conn], self._parts[conn], self.status[conn] = ms._pending, ms._parts, ms.status
+        return units
+
+    def feed(self, reads):
+        for conn, data in reads.items():
+            if not 0 <= conn < self.n_conns:
+                raise ValueError(f"connection {conn} out of range")
+            if self.status[conn] not in (0, _lib.FWS_ERR_CAPACITY):
+                raise FwsError(f"MessageMux.feed after an error on connection {conn}", self.status[conn])
+            if len(data) > self.max_read:
+                raise ValueError(f"a read of {len(data)} bytes exceeds max_read = {self.max_read}")
+        conns = list(reads)
+        n = len(conns)
+        if n == 0:
+            return {}
+        bufs = [self._pending[c] + bytes(reads[c]) for c in conns]
+        if max(map(len, bufs)) > self.slot:
+            raise ValueError("a frame exceeds max_frame: the unfinished frame and the read do not fit the buffer")
+        sz, hw = self._sizes, self._h["wire"].numpy()
+        desc = np.zeros(n, dtype=MSG_READ)
+        for i, (c, buf) in enumerate(zip(conns, bufs)):
+            hw[i * self.slot:i * self.slot + len(buf)] = np.frombuffer(buf, dtype=np.uint8)
+            desc[i] = (i * self.slot, i * self.slot, i * self.slot, len(buf), c, self.slot, self.slot,
+                       i * self.cap, self.cap, i * self.cap, self.cap, 0)
+        self._h["reads"].numpy()[:n * sz["reads"]] = desc.view(np.uint8)
+        stream = torch.cuda.current_stream(self.dev)
+        for k in ("wire", "reads"):
+            self._d[k][:n * sz[k]].copy_(self._h[k][:n * sz[k]], non_blocking=True)
+        max_len = max(1, max(map(len, bufs)))
+        d = self._d
+        check("fws_gpu_decode_messages_multi",
+              decode_messages_multi(self.ctx, d["wire"], d["reads"], n, max_len, d["frames"], d["msgs"], d["dst"],
+                                    d["ctl"], d["res"], d["mres"], self.carries, self.n_conns, stream=stream))
+        for k in ("mres", "msgs", "dst", "ctl"):
+            self._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
+        stream.synchronize()
+        mres = np.frombuffer(self._h["mres"].numpy()[:n * sz["mres"]].tobytes(), dtype=MSG_RESULT)
+        out = {}
+        for i, (c, buf) in enumerate(zip(conns, bufs)):
+            r = mres[i]
+            if int(r["status"]) == _lib.FWS_ERR_DECLINED:
+                out[c] = self._fallback(c, buf)
+                continue
+            entries = np.frombuffer(self._h["msgs"].numpy()[i * sz["msgs"]:i * sz["msgs"] + int(r["n_msgs"]) *
+                                                            MSG_INFO.itemsize].tobytes(), dtype=MSG_INFO)
+            dst = self._h["dst"].numpy()[i * self.slot:(i + 1) * self.slot]
+            ctl = self._h["ctl"].numpy()[i * self.slot:(i + 1) * self.slot]
+            units = []
+            for e in entries:
+                off, ln = int(e["off"]), int(e["len"])
+                if e["opcode"] >= 8:
+                    units.append((int(e["opcode"]), ctl[off:off + ln].tobytes(), False))
+                    continue
+                body = dst[off:off + ln].tobytes()
+                if e["flags"] & _lib.FWS_MSG_CONTINUED:
+                    body = b"".join(self._parts[c]) + body
+                self._parts[c] = []
+                units.append((int(e["opcode"]), body, bool(e["utf8_ok"])))
+            if int(r["open_opcode"]) and int(r["open_len"]):
+                off = int(r["open_off"])
+                self._parts[c].append(dst[off:off + int(r["open_len"])].tobytes())
+            self._pending[c] = buf[int(r["resume_off"]):]
+            self.status[c] = int(r["status"])
+            out[c] = units
+        return out
 
 
 class DecodeEngine:

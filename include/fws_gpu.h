@@ -53,6 +53,8 @@ enum {
     FWS_ERR_INVALID = -21,      /* bad argument / not initialised */
     FWS_ERR_NO_DEVICE = -22,    /* no gfx950 device visible */
     FWS_ERR_INTERNAL = -23,     /* device-side failure (decode grid barrier timed out) */
+    FWS_ERR_DECLINED = -24,     /* fws_gpu_decode_messages_multi, per read: the read is outside the
+                                   one-launch form's limits; run fws_gpu_decode_messages_carry on it */
     FWS_ERR_HIP_BASE = -1000    /* -1000 - hipError_t */
 };
 
@@ -356,6 +358,69 @@ int fws_gpu_decode_messages_carry(fws_gpu_ctx *ctx, const void *dev_wire, uint64
                                   void *dev_ctl, uint64_t ctl_cap,
                                   fws_decode_result *dev_result, fws_msg_result *dev_msg_result,
                                   fws_msg_carry *dev_carry, void *stream);
+
+/* ---- the same for the reads of many connections in one launch --------------
+ * A server's loop step brings reads of a few KiB from many connections;
+ * fws_gpu_decode_messages_carry is a sequence of launches per connection.
+ * fws_gpu_decode_messages_multi decodes n reads in one launch, one workgroup
+ * per read, the read staged in on-chip memory. Each read is described by a
+ * fws_msg_read in device memory: where its bytes, its output regions and its
+ * slices of the frame and entry arrays lie, and which carry is its
+ * connection's. */
+#define FWS_MSG_MULTI_MAX_READ   (128u << 10)   /* bytes of one read */
+#define FWS_MSG_MULTI_MAX_FRAMES 256u           /* headers in one read */
+
+typedef struct fws_msg_read {       /* device memory, one per read */
+    uint64_t wire_off;              /* the read's bytes in dev_wire, 16-B aligned */
+    uint64_t dst_off;               /* its region of dev_dst, 16-B aligned */
+    uint64_t ctl_off;               /* its region of dev_ctl, any alignment */
+    uint32_t len;                   /* bytes of wire (0 allowed) */
+    uint32_t conn;                  /* index into dev_carries, < n_conns; distinct within a call */
+    uint32_t dst_cap, ctl_cap;      /* bytes */
+    uint32_t frame_base, frame_cap; /* its slice of dev_frames */
+    uint32_t msg_base, msg_cap;     /* its slice of dev_msgs */
+    uint64_t reserved;              /* 0 */
+} fws_msg_read;                     /* 64 bytes */
+
+/* For read r, everything the call writes -- its frame slice, its entries, its
+ * regions of dev_dst and dev_ctl, dev_results[r], dev_msg_results[r] and
+ * dev_carries[conn] -- is byte for byte what fws_gpu_decode_messages_carry
+ * writes for the same bytes, the same four capacities and the same carry, with
+ * every offset and index relative to the read (hdr_off, fws_msg_info.off,
+ * first_frame, resume_off, open_off ...). One exception:
+ * fws_decode_result.n_survivors, a diagnostic, is n_frames. The contract of
+ * fws_gpu_decode_messages_carry above holds per read unchanged.
+ *   isolation   an error on one connection -- protocol, sequencing, capacity --
+ *             changes nothing for any other. The call returns 0 whenever the
+ *             launch was made; per-read outcomes are dev_msg_results[r].status.
+ *   declined    a read with len > max_len, len > FWS_MSG_MULTI_MAX_READ or more
+ *             than FWS_MSG_MULTI_MAX_FRAMES headers: both results get status =
+ *             FWS_ERR_DECLINED and every other field zero, but err_frame and
+ *             open_first_frame = 0xFFFFFFFF; nothing else is written for that
+ *             read and its carry is untouched. The caller runs
+ *             fws_gpu_decode_messages_carry on the same bytes with the same
+ *             carry and the connection continues exactly.
+ *   descriptors a misaligned wire_off or dst_off, or conn >= n_conns: both
+ *             results get FWS_ERR_INVALID in the same way. Two reads of one call
+ *             that name the same conn are a contract violation: the result is
+ *             undefined for that connection only.
+ *   max_len   the caller's upper bound on len (it built the descriptors),
+ *             between 1 and FWS_MSG_MULTI_MAX_READ. It selects the kernel form:
+ *             up to 16 KiB a small workgroup, several to a compute unit; above,
+ *             one workgroup to a compute unit.
+ *   ordering  stream-ordered: no host synchronisation, no device-to-host copy;
+ *             no workspace, so nothing is allocated, with or without
+ *             fws_gpu_ctx_reserve. Two calls queued on one stream chain through
+ *             the carries; a captured call needs no reset node.
+ * n == 0 returns 0 without a launch. Otherwise ctx and every pointer must be
+ * non-null, dev_wire and dev_dst 16-B aligned and max_len in range, or the call
+ * returns FWS_ERR_INVALID before any device call. Out of scope as above. */
+int fws_gpu_decode_messages_multi(fws_gpu_ctx *ctx, const void *dev_wire,
+                                  const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                  fws_frame_info *dev_frames, fws_msg_info *dev_msgs,
+                                  void *dev_dst, void *dev_ctl,
+                                  fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
+                                  fws_msg_carry *dev_carries, uint32_t n_conns, void *stream);
 
 /* ---- batched stream decode: many independent streams ----------------------
  * fws_gpu_decode_stream over a list of independent streams (the buffers of

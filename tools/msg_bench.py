@@ -28,8 +28,20 @@ and messages / (parse + gather + utf8). One JSON line per workload.
        fragments (BASELINE config 4's shape). The buffers of both protocols are
        worked out on the host from the frame list and checked against every
        call's resume_off in an untimed pass first.
+--multi measures fws_gpu_decode_messages_multi: n connections
+x one read each of 1 / 4 / 16 / 64 KiB (n in 1, 8, 64, 512, 4096), TEXT messages
+fragmented as workload (b) with payloads up to half the read, every read made
+of whole messages so the carries return to "closed" and every pass is the
+same work. One multi call against the n sequential
+fws_gpu_decode_messages_carry calls on the same reads and carries (that code is
+the parent commit's: the baseline), alternating within each round, and a
+device-to-device copy of the same bytes as a bandwidth reference; max_len is
+the read size, so the small kernel form is the one measured on small reads.
+Before timing, the two paths' outputs are compared byte for byte. Reads repeat
+after 64 distinct ones. One JSON line per grid point.
 usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out FILE]
-       python tools/msg_bench.py --carry [--parent-lib SO] [--read-mib M] [--target MiB] [--out FILE]"""
+       python tools/msg_bench.py --carry [--parent-lib SO] [--read-mib M] [--target MiB] [--out FILE]
+       python tools/msg_bench.py --multi [--grid-n N,N,..] [--grid-kib K,K,..] [--rounds R] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -289,6 +301,114 @@ def carry_reads(name, wire, read_bytes, rounds, seed=11):
     return out
 
 
+def multi_read(rng, size):
+    """One read of exactly `size` bytes (>= 1 KiB): whole TEXT messages in 2 to 8
+    fragments, payloads log-uniform 64 B .. size / 2, a PING every 64 frames, at
+    most 240 frames, the rest filled by one single-frame TEXT message. Returns (bytes, frames)."""
+    parts, total, nf = [], 0, 0
+
+    def put(op, fin, n, form126=False):
+        nonlocal total, nf
+        key = int(rng.integers(0, 1 << 32))
+        h = header(op, fin, n, key)
+        if form126 and n < 126:
+            h = bytes([(fin << 7) | op, 0x80 | 126]) + struct.pack(">H", n) + struct.pack("<I", key)
+        kb = np.resize(np.frombuffer(struct.pack("<I", key), dtype=np.uint8), n)
+        body = rng.integers(0x20, 0x7F, n, dtype=np.uint8) ^ kb if op < 8 else kb
+        parts.append(h + body.tobytes())
+        total += len(h) + n
+        nf += 1
+
+    while True:
+        n = int(np.exp(rng.uniform(np.log(64), np.log(size // 2))))
+        k = int(rng.integers(2, 9))
+        if total + n + 8 * k + 14 + 134 > size or nf + k + 2 > 240:
+            break
+        cuts = np.sort(rng.integers(0, n + 1, k - 1)).tolist()
+        for j, (a, b) in enumerate(zip([0] + cuts, cuts + [n])):
+            if nf % 64 == 63:
+                put(9, 1, 8)
+            put(1 if j == 0 else 0, int(j == k - 1), b - a)
+    rem = size - total                                # >= 134: an 8-byte header
+    put(1, 1, rem - 8, form126=True)
+    wire = b"".join(parts)
+    assert len(wire) == size
+    return wire, nf
+
+
+def multi_bench(n, size, rounds, steps):
+    L = _lib.lib()
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(1000 * n + size)
+    distinct = [multi_read(rng, size) for _ in range(min(n, 64))]
+    cap = max(f for _, f in distinct) + 4
+    assert cap <= _lib.FWS_MSG_MULTI_MAX_FRAMES
+    ctl_cap = 8 * (cap // 64 + 2)
+    host = np.stack([np.frombuffer(w, dtype=np.uint8) for w, _ in distinct])
+    host = host[np.arange(n) % len(distinct)].reshape(-1)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    wire = torch.from_numpy(host).to(dev)
+    dst, dst2 = torch.zeros(n * size, **u8), torch.zeros(n * size, **u8)
+    ctl = torch.zeros(n * ctl_cap, **u8)
+    frames, msgs = torch.zeros(n * cap * 24, **u8), torch.zeros(n * cap * 32, **u8)
+    res, mres, carries = torch.zeros(n * 40, **u8), torch.zeros(n * 64, **u8), torch.zeros(n * 64, **u8)
+    desc = np.zeros(n, dtype=_lib.MSG_READ)
+    for r in range(n):
+        desc[r] = (r * size, r * size, r * ctl_cap, size, r, size, ctl_cap, r * cap, cap, r * cap, cap, 0)
+    reads = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    ctx = gpu.Ctx(0, max_frames=cap, max_stream_bytes=size)
+    s = torch.cuda.current_stream()
+    seq = L.fws_gpu_decode_messages_carry
+    p = {k: t.data_ptr() for k, t in dict(wire=wire, dst=dst, ctl=ctl, frames=frames, msgs=msgs, res=res, mres=mres,
+                                          carries=carries).items()}
+
+    def f_multi(i):
+        assert gpu.decode_messages_multi(ctx, wire, reads, n, size, frames, msgs, dst, ctl, res, mres, carries, n) == 0
+
+    def f_seq(i):
+        h = s.cuda_stream
+        for r in range(n):
+            rc = seq(ctx.h, p["wire"] + r * size, size, p["frames"] + r * cap * 24, cap, p["msgs"] + r * cap * 32, cap,
+                     p["dst"] + r * size, size, p["ctl"] + r * ctl_cap, ctl_cap, p["res"] + r * 40,
+                     p["mres"] + r * 64, p["carries"] + r * 64, h)
+            assert rc == 0
+
+    def f_copy(i):
+        dst2.copy_(wire)
+
+    # checked first: both paths write the same bytes (n_survivors, a diagnostic, apart)
+    snaps = []
+    for f in (f_multi, f_seq):
+        for t in (dst, ctl, frames, msgs, res, mres, carries):
+            t.zero_()
+        f(0)
+        torch.cuda.synchronize()
+        r = np.frombuffer(res.cpu().numpy().tobytes(), dtype=_lib.DECODE_RESULT).copy()
+        r["n_survivors"] = 0
+        snaps.append([t.clone() for t in (dst, ctl, frames, msgs, mres, carries)] + [r])
+    m = np.frombuffer(snaps[0][4].cpu().numpy().tobytes(), dtype=_lib.MSG_RESULT)
+    assert (m["status"] == 0).all() and (m["resume_off"] == size).all() and (m["open_opcode"] == 0).all()
+    for a, b in zip(snaps[0][:-1], snaps[1][:-1]):
+        assert torch.equal(a, b), "the multi call and the sequential calls differ"
+    assert (snaps[0][-1] == snaps[1][-1]).all()
+    forms = {"multi": (f_multi, steps), "seq": (f_seq, max(1, min(steps, 2048 // n))), "copy": (f_copy, steps)}
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(timed(forms[k][0], forms[k][1], warm=2 if k == "seq" else 10))
+    out = {"measure": "multi", "n": n, "read_bytes": size, "form": "small" if size <= (16 << 10) else "full",
+           "wire_bytes": n * size, "frames_per_read_max": cap - 4, "messages": int(m["n_msgs"].sum()),
+           "rounds": rounds, "steps": {k: v[1] for k, v in forms.items()}, "device": torch.cuda.get_device_name(0)}
+    for k in forms:
+        out[k + "_us"] = round(statistics.median(times[k]), 2)
+        out[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    out["seq_over_multi"] = round(out["seq_us"] / out["multi_us"], 2)
+    out["multi_over_copy"] = round(out["multi_us"] / out["copy_us"], 2)
+    out["multi_wire_gb_s"] = round(n * size / out["multi_us"] / 1e3, 2)
+    ctx.close()
+    return out
+
+
 def c3_stream(target):
     wire, descs, _ = gpu.config_c3(target=target)
     regions = np.zeros(len(descs), dtype=_lib.FRAME_DESC)
@@ -387,9 +507,21 @@ def main():
     ap.add_argument("--carry", action="store_true", help="measure fws_gpu_decode_messages_carry (see above)")
     ap.add_argument("--parent-lib", default="", help="libfws_gpu.so built from the parent commit, for (i)")
     ap.add_argument("--read-mib", type=float, default=2.0)
+    ap.add_argument("--multi", action="store_true", help="measure fws_gpu_decode_messages_multi (see above)")
+    ap.add_argument("--grid-n", default="1,8,64,512,4096", help="--multi: connections")
+    ap.add_argument("--grid-kib", default="1,4,16,64", help="--multi: read sizes, KiB")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.multi:
+        for kib in map(int, a.grid_kib.split(",")):
+            for n in map(int, a.grid_n.split(",")):
+                lines.append(json.dumps(multi_bench(n, kib << 10, a.rounds, a.steps)))
+                print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.carry:
         wire, _, _, n_frames = fragmented_stream(target)
         if a.parent_lib:
