@@ -64,6 +64,12 @@ MSG_READ = np.dtype([("wire_off", "<u8"), ("dst_off", "<u8"), ("ctl_off", "<u8")
                      ("dst_cap", "<u4"), ("ctl_cap", "<u4"), ("frame_base", "<u4"), ("frame_cap", "<u4"),
                      ("msg_base", "<u4"), ("msg_cap", "<u4"), ("reserved", "<u8")])
 assert MSG_READ.itemsize == 64
+# fws_gpu_decode_messages_flow: the connection's state, fws_msg_carry (the fields of MSG_CARRY) and the frame in
+# progress; FWS_MSG_FLOW_MAX_PENDING bounds what a call leaves unconsumed (a partial header or a cut control frame)
+MSG_FLOW = np.dtype([("msg", MSG_CARRY), ("frame_unread", "<u8"), ("frame_len", "<u8"), ("frame_key", "<u4"),
+                     ("frame_fin", "u1"), ("pad", "u1", (3,)), ("reserved", "<u8")])
+assert MSG_FLOW.itemsize == 96 and MSG_FLOW.fields["frame_unread"][1] == MSG_CARRY.itemsize
+FWS_MSG_FLOW_MAX_PENDING = 14 + 125 - 1
 RX_EVENT = np.dtype([("kind", "<u4"), ("opcode", "<u4"), ("is_ctl", "u1"), ("frame_end", "u1"),
                      ("msg_end", "u1"), ("fin", "u1"), ("code", "<u4"), ("size", "<u8"),
                      ("data_off", "<u8"), ("ctl_off", "<u8"), ("capacity", "<u8")])
@@ -116,6 +122,7 @@ SIGNATURES = [
     ("fws_gpu_decode_messages", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P]),
     ("fws_gpu_decode_messages_carry", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P, _P]),
     ("fws_gpu_decode_messages_multi", _I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P]),
+    ("fws_gpu_decode_messages_flow", _I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P]),
     ("fws_gpu_validate_utf8", _I, [_P, _P, _P, _U32, _P, _P]),
     ("fws_rx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_rx_session_destroy", None, [_P]),

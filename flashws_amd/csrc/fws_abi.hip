@@ -483,6 +483,22 @@ int fws_gpu_decode_messages_multi(fws_gpu_ctx *ctx, const void *dev_wire, const 
                                 n_conns, (hipStream_t)stream);
 }
 
+int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire, const fws_msg_read *dev_reads, uint32_t n,
+                                 uint32_t max_len, fws_frame_info *dev_frames, fws_msg_info *dev_msgs, void *dev_dst,
+                                 void *dev_ctl, fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
+                                 fws_msg_flow *dev_flows, uint32_t n_conns, void *stream) {
+    if (n == 0) return 0;
+    if (!ctx || !dev_wire || !dev_reads || !dev_frames || !dev_msgs || !dev_dst || !dev_ctl || !dev_results ||
+        !dev_msg_results || !dev_flows)
+        return FWS_ERR_INVALID;
+    if ((((uintptr_t)dev_wire | (uintptr_t)dev_dst) & 15u) != 0) return FWS_ERR_INVALID;
+    if (max_len < 1u || max_len > FWS_MSG_MULTI_MAX_READ) return FWS_ERR_INVALID;
+    if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
+    return fws_launch_msg_flow((const uint8_t *)dev_wire, dev_reads, n, max_len, dev_frames, dev_msgs,
+                               (uint8_t *)dev_dst, (uint8_t *)dev_ctl, dev_results, dev_msg_results, dev_flows,
+                               n_conns, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 int fws_decode_prepare(fws_gpu_ctx *ctx, uint64_t len, uint32_t cap, bool utf8) {

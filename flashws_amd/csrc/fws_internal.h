@@ -339,6 +339,11 @@ int fws_launch_msg_multi(const uint8_t *wire, const fws_msg_read *reads, uint32_
                          fws_frame_info *frames, fws_msg_info *msgs, uint8_t *dst, uint8_t *ctl,
                          fws_decode_result *res, fws_msg_result *mres, fws_msg_carry *carries, uint32_t n_conns,
                          hipStream_t s);
+// fws_gpu_decode_messages_flow (msg_flow_kernels.hip): the same with a data frame in progress in the state
+int fws_launch_msg_flow(const uint8_t *wire, const fws_msg_read *reads, uint32_t n, uint32_t max_len,
+                        fws_frame_info *frames, fws_msg_info *msgs, uint8_t *dst, uint8_t *ctl,
+                        fws_decode_result *res, fws_msg_result *mres, fws_msg_flow *flows, uint32_t n_conns,
+                        hipStream_t s);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
                        hipStream_t s, const uint32_t *deny = nullptr);

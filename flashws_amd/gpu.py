@@ -443,6 +443,137 @@ class MessageMux:
         return out
 
 
+def decode_messages_flow(ctx, wire, reads, n, max_len, frames, msgs, dst, ctl, results, msg_results, flows,
+                         n_conns, stream=None):
+    """fws_gpu_decode_messages_flow: decode_messages_multi with a state per
+    connection that also holds a data frame in progress, so a read may begin
+    and end inside a frame's payload. flows holds n_conns fws_msg_flow records
+    (_lib.MSG_FLOW, zeros for new connections) in a device uint8 tensor; the
+    other arguments are decode_messages_multi's. Returns the call's status;
+    nothing is synchronised."""
+    return lib().fws_gpu_decode_messages_flow(ctx.h, _ptr(wire), _ptr(reads), n, max_len, _ptr(frames), _ptr(msgs),
+                                              _ptr(dst), _ptr(ctl), _ptr(results), _ptr(msg_results),
+                                              _ptr(flows), n_conns, _stream_handle(stream))
+
+
+def read_msg_flow(flows, conn=0):
+    sz = _lib.MSG_FLOW.itemsize
+    return np.frombuffer(flows[conn * sz:(conn + 1) * sz].cpu().numpy().tobytes(), dtype=_lib.MSG_FLOW)[0]
+
+
+class MessageFlow:
+    """MessageMux without a frame limit: feed({conn: bytes, ...}) makes one
+    fws_gpu_decode_messages_flow call and one synchronisation for all
+    connections and returns {conn: [(opcode, bytes, utf8_ok), ...]}, the units
+    each connection completed, in order. A data frame's payload is decoded as
+    it arrives, so a frame may be of any size and is uploaded once; what is
+    kept in front of the next read is at most a partial header or a cut control
+    frame (_lib.FWS_MSG_FLOW_MAX_PENDING bytes). The parts of a message that
+    arrives over several reads are joined at its FWS_MSG_CONTINUED entry. A
+    read with more headers than one call takes (FWS_ERR_CAPACITY with
+    progress) is continued from resume_off by further calls for that
+    connection inside the same feed; there is no other path. A connection
+    whose status is a protocol or sequencing error keeps it in status[conn];
+    feeding it again raises, the others go on. max_read bounds one
+    connection's feed."""
+
+    def __init__(self, ctx, n_conns, max_read, device="cuda:0"):
+        self.ctx, self.n_conns, self.max_read = ctx, n_conns, max_read
+        if max_read + _lib.FWS_MSG_FLOW_MAX_PENDING > _lib.FWS_MSG_MULTI_MAX_READ:
+            raise ValueError("max_read exceeds FWS_MSG_MULTI_MAX_READ - 138")
+        self.slot = (max_read + _lib.FWS_MSG_FLOW_MAX_PENDING + 15) & ~15
+        self.cap = min(self.slot // 6 + 1, _lib.FWS_MSG_MULTI_MAX_FRAMES)
+        self.msg_cap = self.cap + 1                   # a lead that completes a message, then one per frame
+        self.dev = torch.device(device)
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        pin = dict(dtype=torch.uint8, pin_memory=True)
+        self._sizes = dict(wire=self.slot, dst=self.slot, ctl=self.slot, frames=self.cap * FRAME_INFO.itemsize,
+                           msgs=self.msg_cap * MSG_INFO.itemsize, res=DECODE_RESULT.itemsize,
+                           mres=MSG_RESULT.itemsize, reads=MSG_READ.itemsize)
+        self._d = {k: torch.zeros(n_conns * sz, **u8) for k, sz in self._sizes.items()}
+        self._h = {k: torch.zeros(n_conns * sz, **pin) for k, sz in self._sizes.items()}
+        self.flows = torch.zeros(n_conns * _lib.MSG_FLOW.itemsize, **u8)
+        self._pending = [b""] * n_conns
+        self._parts = [[] for _ in range(n_conns)]
+        self.status = [0] * n_conns
+        self.calls = 0                                # fws_gpu_decode_messages_flow calls made
+        self.uploaded = [0] * n_conns                 # wire bytes copied to the device, per connection
+
+    def _call(self, bufs):
+        """One launch for {conn: bytes}: the units per connection; pending, parts and status updated."""
+        conns, n = list(bufs), len(bufs)
+        sz, hw = self._sizes, self._h["wire"].numpy()
+        desc = np.zeros(n, dtype=MSG_READ)
+        for i, c in enumerate(conns):
+            buf = bufs[c]
+            hw[i * self.slot:i * self.slot + len(buf)] = np.frombuffer(buf, dtype=np.uint8)
+            desc[i] = (i * self.slot, i * self.slot, i * self.slot, len(buf), c, self.slot, self.slot,
+                       i * self.cap, self.cap, i * self.msg_cap, self.msg_cap, 0)
+            self.uploaded[c] += len(buf)
+        self._h["reads"].numpy()[:n * sz["reads"]] = desc.view(np.uint8)
+        stream = torch.cuda.current_stream(self.dev)
+        for k in ("wire", "reads"):
+            self._d[k][:n * sz[k]].copy_(self._h[k][:n * sz[k]], non_blocking=True)
+        max_len = max(1, max(map(len, bufs.values())))
+        d = self._d
+        check("fws_gpu_decode_messages_flow",
+              decode_messages_flow(self.ctx, d["wire"], d["reads"], n, max_len, d["frames"], d["msgs"], d["dst"],
+                                   d["ctl"], d["res"], d["mres"], self.flows, self.n_conns, stream=stream))
+        self.calls += 1
+        for k in ("mres", "msgs", "dst", "ctl"):
+            self._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
+        stream.synchronize()
+        mres = np.frombuffer(self._h["mres"].numpy()[:n * sz["mres"]].tobytes(), dtype=MSG_RESULT)
+        out = {}
+        for i, c in enumerate(conns):
+            r, buf = mres[i], bufs[c]
+            status = int(r["status"])
+            if status in (_lib.FWS_ERR_DECLINED, _lib.FWS_ERR_INVALID):
+                raise FwsError(f"fws_gpu_decode_messages_flow refused the read of connection {c}", status)
+            entries = np.frombuffer(self._h["msgs"].numpy()[i * sz["msgs"]:i * sz["msgs"] + int(r["n_msgs"]) *
+                                                            MSG_INFO.itemsize].tobytes(), dtype=MSG_INFO)
+            dst = self._h["dst"].numpy()[i * self.slot:(i + 1) * self.slot]
+            ctl = self._h["ctl"].numpy()[i * self.slot:(i + 1) * self.slot]
+            units = []
+            for e in entries:
+                off, ln = int(e["off"]), int(e["len"])
+                if e["opcode"] >= 8:
+                    units.append((int(e["opcode"]), ctl[off:off + ln].tobytes(), False))
+                    continue
+                body = dst[off:off + ln].tobytes()
+                if e["flags"] & _lib.FWS_MSG_CONTINUED:
+                    body = b"".join(self._parts[c]) + body
+                self._parts[c] = []
+                units.append((int(e["opcode"]), body, bool(e["utf8_ok"])))
+            if int(r["open_opcode"]) and int(r["open_len"]):
+                off = int(r["open_off"])
+                self._parts[c].append(dst[off:off + int(r["open_len"])].tobytes())
+            self._pending[c] = buf[int(r["resume_off"]):]
+            self.status[c] = status
+            out[c] = (units, int(r["resume_off"]))
+        return out
+
+    def feed(self, reads):
+        for conn, data in reads.items():
+            if not 0 <= conn < self.n_conns:
+                raise ValueError(f"connection {conn} out of range")
+            if self.status[conn] not in (0, _lib.FWS_ERR_CAPACITY):
+                raise FwsError(f"MessageFlow.feed after an error on connection {conn}", self.status[conn])
+            if len(data) > self.max_read:
+                raise ValueError(f"a read of {len(data)} bytes exceeds max_read = {self.max_read}")
+        bufs = {c: self._pending[c] + bytes(reads[c]) for c in reads}
+        out = {c: [] for c in reads}
+        while bufs:
+            again = {}
+            for c, (units, resume) in self._call(bufs).items():
+                out[c] += units
+                # more headers than one call takes: the rest of the same bytes, from resume_off
+                if self.status[c] == _lib.FWS_ERR_CAPACITY and resume > 0 and self._pending[c]:
+                    again[c] = self._pending[c]
+            bufs = again
+        return out
+
+
 class DecodeEngine:
     """fws_decode_engine: fws_gpu_decode_stream over many independent streams,
     decodes kept in flight on two HIP streams. mode / scan_cus select the

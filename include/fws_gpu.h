@@ -422,6 +422,94 @@ int fws_gpu_decode_messages_multi(fws_gpu_ctx *ctx, const void *dev_wire,
                                   fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
                                   fws_msg_carry *dev_carries, uint32_t n_conns, void *stream);
 
+/* ---- the same, resuming inside a frame: any cut, frames of any size ---------
+ * The calls above take whole frames, so a frame has to fit in the bytes of one
+ * call. OnRecvData hands out a frame's payload as it arrives (unread_pl_len_
+ * and the rotated key, w_socket.h:223-245, 756-759) and accepts frames up to
+ * 2^32 B (w_socket.h:493-498). fws_gpu_decode_messages_flow is the one-launch,
+ * many-connections call with a state per connection that also holds a data
+ * frame in progress: a read may begin inside a data frame's payload and end
+ * inside one. */
+typedef struct fws_msg_flow {      /* device memory; all zero = a new connection */
+    fws_msg_carry msg;             /* exactly what fws_gpu_decode_messages_carry keeps */
+    uint64_t frame_unread;         /* payload bytes of the data frame in progress still to come; 0: between frames */
+    uint64_t frame_len;            /* that frame's payload_len (0 when frame_unread == 0) */
+    uint32_t frame_key;            /* its key rotated to the next byte to come: rotr(key, 8 * (delivered & 3)),
+                                      the reference's RotateR (w_socket.h:756-759), fws_rx_state.mask_key */
+    uint8_t  frame_fin;            /* its FIN bit */
+    uint8_t  pad[3];               /* 0 */
+    uint64_t reserved;             /* 0 */
+} fws_msg_flow;                    /* 96 bytes */
+
+/* Arguments, alignment rules, the argument checks before any device call,
+ * n == 0, the fws_msg_read descriptor, the kernel form chosen by max_len,
+ * isolation, stream ordering and the absence of a workspace are those of
+ * fws_gpu_decode_messages_multi; offsets and indices are relative to the read.
+ * With frame_unread == 0 and a read of whole frames every byte written equals
+ * that call's (dev_flows[conn].msg its carry, the frame fields zero). What
+ * differs:
+ *   input     a read's bytes are what was left from the previous call's
+ *             resume_off, then the new bytes. With frame_unread > 0 the first
+ *             lead = min(frame_unread, len) bytes are payload of the frame in
+ *             progress and the header chain starts at lead; else at 0.
+ *   data frames are taken as they arrive: a data frame with a complete header is
+ *             sequence-checked against the open state, then its present bytes
+ *             (zero allowed) are gathered and counted even when the payload runs
+ *             past the end. The state then records frame_unread / frame_len /
+ *             frame_key / frame_fin, the message stays open, resume_off = len;
+ *             the present bytes belong to the open part (open_off / open_len).
+ *             A frame counts in n_data_frames, open_frames and the entries in
+ *             the call that holds its header; the lead counts bytes only.
+ *   the lead  goes to dev_dst from offset 0, unmasked with frame_key from phase
+ *             0. If it ends the frame (frame_unread <= len) and frame_fin is
+ *             set, the message completes there with a FWS_MSG_CONTINUED entry:
+ *             off = 0, len and n_data_frames this call's part, first_frame /
+ *             last_frame the message's first and last data frames whose header
+ *             is in this call, 0xFFFFFFFF if none. With frame_fin = 0 the chain
+ *             goes on with the message open. If it does not end the frame the
+ *             read is all payload: n_frames = 0, frame_unread shrinks by len,
+ *             frame_key is rotated by len & 3.
+ *   control frames stay whole: one whose payload is cut is not processed and
+ *             resume_off is its header; an incomplete trailing header is left
+ *             as well. A caller's pending bytes are fewer than 14 + 125.
+ *   dev_frames / fws_decode_result describe the headers in this read: hdr_off
+ *             relative to the read start (lead included), FWS_FRAME_TRUNCATED on
+ *             a cut last frame, carry_unread the bytes still to come of whatever
+ *             frame is in progress at the end, consumed = len unless a partial
+ *             header remains or an error or the header limit stopped the walk.
+ *   UTF-8     as fws_gpu_decode_messages_carry: each call's part starts at
+ *             dev_dst + 0, utf8_tail is its left context, utf8_bad is sticky;
+ *             the final verdict is exact wherever the cuts fell, inside a frame
+ *             and inside a sequence included.
+ *   headers   no read is declined for its header count. At header number
+ *             FWS_MSG_MULTI_MAX_FRAMES + 1 the walk stops as at an exceeded
+ *             frame_cap: the first min(frame_cap, FWS_MSG_MULTI_MAX_FRAMES)
+ *             frames are processed, n_frames counts the headers parsed (at most
+ *             FWS_MSG_MULTI_MAX_FRAMES + 1), consumed is that header's offset,
+ *             status = FWS_ERR_CAPACITY unless there is an earlier problem, the
+ *             state and resume_off are valid and the caller continues from
+ *             resume_off. FWS_ERR_DECLINED remains for len > max_len or len >
+ *             FWS_MSG_MULTI_MAX_READ; FWS_ERR_INVALID per descriptor as above.
+ *   errors    a sequencing or control-frame-form error at frame e gives the
+ *             state just before e (frame_unread = 0: e is a header). A cut data
+ *             frame that fails the sequence check is an error and is not taken.
+ *   capacity  data_bytes > dst_cap, ctl_bytes > ctl_cap or n_msgs > msg_cap:
+ *             nothing is written to dev_dst / dev_ctl, the whole 96-byte state
+ *             is left exactly as found and resume_off = 0. A call never
+ *             produces more data bytes than it was given: dst_cap >= len is
+ *             always enough.
+ * A read longer than FWS_MSG_MULTI_MAX_READ is cut anywhere into pieces whose
+ * calls are queued on one stream; they chain through dev_flows without the
+ * host. Out of scope: the same for fws_gpu_decode_messages(_carry), UTF-8
+ * validation of CLOSE reasons, client-side streams, the C++ adapter and the
+ * FLoop hook. */
+int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire,
+                                 const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                 fws_frame_info *dev_frames, fws_msg_info *dev_msgs,
+                                 void *dev_dst, void *dev_ctl,
+                                 fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
+                                 fws_msg_flow *dev_flows, uint32_t n_conns, void *stream);
+
 /* ---- batched stream decode: many independent streams ----------------------
  * fws_gpu_decode_stream over a list of independent streams (the buffers of
  * many connections, or successive batches of one: FLoop's loop hands each

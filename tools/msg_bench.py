@@ -39,9 +39,23 @@ device-to-device copy of the same bytes as a bandwidth reference; max_len is
 the read size, so the small kernel form is the one measured on small reads.
 Before timing, the two paths' outputs are compared byte for byte. Reads repeat
 after 64 distinct ones. One JSON line per grid point.
+--flow measures fws_gpu_decode_messages_flow:
+  (i)  flow_cost    the --multi grid's whole-message reads (1 / 4 / 16 / 64 KiB x
+       n = 1, 64, 512) through the flow call and this tree's multi call against
+       the multi call of a library built from the parent commit (--parent-lib),
+       two contexts of which give the A/A spread; the forms alternate within
+       every round, and every form's outputs are compared byte for byte first.
+  (ii) flow_frames  n connections each receive one 1 MiB frame in 16 KiB reads:
+       the flow protocol (every read uploaded once, one launch per step for all
+       connections) against the only alternative today, the frame kept on the
+       host and the carry call run on the growing buffer after every read.
+       Total stream time per pass, uploads included, and bytes uploaded per
+       connection; the flow parts joined are checked against the carry call's
+       message first.
 usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out FILE]
        python tools/msg_bench.py --carry [--parent-lib SO] [--read-mib M] [--target MiB] [--out FILE]
-       python tools/msg_bench.py --multi [--grid-n N,N,..] [--grid-kib K,K,..] [--rounds R] [--out FILE]"""
+       python tools/msg_bench.py --multi [--grid-n N,N,..] [--grid-kib K,K,..] [--rounds R] [--out FILE]
+       python tools/msg_bench.py --flow [--parent-lib SO] [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -409,6 +423,181 @@ def multi_bench(n, size, rounds, steps):
     return out
 
 
+def flow_cost(n, size, parent_lib, rounds, steps):
+    """--flow (i): multi_bench's whole-message reads through the flow call, this
+    tree's multi call and the parent library's multi call (two contexts: A/A)."""
+    dev = torch.device("cuda:0")
+    P = C.CDLL(parent_lib)
+    for name, res_t, args in _lib.SIGNATURES:
+        if hasattr(P, name):
+            getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
+    assert not hasattr(P, "fws_gpu_decode_messages_flow"), "--parent-lib is this tree's library"
+    rng = np.random.default_rng(1000 * n + size)
+    distinct = [multi_read(rng, size) for _ in range(min(n, 64))]
+    cap = max(f for _, f in distinct) + 4
+    ctl_cap = 8 * (cap // 64 + 2)
+    host = np.stack([np.frombuffer(w, dtype=np.uint8) for w, _ in distinct])
+    host = host[np.arange(n) % len(distinct)].reshape(-1)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    wire = torch.from_numpy(host).to(dev)
+    dst, ctl = torch.zeros(n * size, **u8), torch.zeros(n * ctl_cap, **u8)
+    frames, msgs = torch.zeros(n * cap * 24, **u8), torch.zeros(n * cap * 32, **u8)
+    res, mres = torch.zeros(n * 40, **u8), torch.zeros(n * 64, **u8)
+    carries, flows = torch.zeros(n * 64, **u8), torch.zeros(n * _lib.MSG_FLOW.itemsize, **u8)
+    desc = np.zeros(n, dtype=_lib.MSG_READ)
+    for r in range(n):
+        desc[r] = (r * size, r * size, r * ctl_cap, size, r, size, ctl_cap, r * cap, cap, r * cap, cap, 0)
+    reads = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    ctx = gpu.Ctx(0)
+    s = torch.cuda.current_stream()
+    pctx = []
+    for _ in range(2):
+        h = C.c_void_p()
+        assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0
+        pctx.append(h)
+
+    def parent(h):
+        def f(i):
+            assert P.fws_gpu_decode_messages_multi(h, wire.data_ptr(), reads.data_ptr(), n, size, frames.data_ptr(),
+                                                   msgs.data_ptr(), dst.data_ptr(), ctl.data_ptr(), res.data_ptr(),
+                                                   mres.data_ptr(), carries.data_ptr(), n, s.cuda_stream) == 0
+        return f
+
+    def f_multi(i):
+        assert gpu.decode_messages_multi(ctx, wire, reads, n, size, frames, msgs, dst, ctl, res, mres, carries, n) == 0
+
+    def f_flow(i):
+        assert gpu.decode_messages_flow(ctx, wire, reads, n, size, frames, msgs, dst, ctl, res, mres, flows, n) == 0
+
+    forms = {"parent_a": parent(pctx[0]), "parent_b": parent(pctx[1]), "multi": f_multi, "flow": f_flow}
+    want = None
+    for k, f in forms.items():                        # checked first: every form writes the same bytes
+        for t in (dst, ctl, frames, msgs, res, mres, carries, flows):
+            t.zero_()
+        f(0)
+        torch.cuda.synchronize()
+        state = flows.view(n, -1)[:, :64].reshape(-1) if k == "flow" else carries
+        got = [t.clone() for t in (dst, ctl, frames, msgs, res, mres, state)]
+        want = want or got
+        assert all(torch.equal(a, b) for a, b in zip(got, want)), k
+    m = np.frombuffer(mres.cpu().numpy().tobytes(), dtype=_lib.MSG_RESULT)
+    assert (m["status"] == 0).all() and (m["resume_off"] == size).all() and (m["open_opcode"] == 0).all()
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(timed(forms[k], steps))
+    out = {"measure": "flow_cost", "n": n, "read_bytes": size, "form": "small" if size <= (16 << 10) else "full",
+           "wire_bytes": n * size, "rounds": rounds, "steps": steps, "device": torch.cuda.get_device_name(0),
+           "parent_lib": os.path.basename(parent_lib)}
+    for k in forms:
+        out[k + "_us"] = round(statistics.median(times[k]), 2)
+        out[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    base = min(out["parent_a_us"], out["parent_b_us"])
+    out["aa_spread_us"] = round(abs(out["parent_a_us"] - out["parent_b_us"]), 2)
+    out["flow_minus_parent_us"] = round(out["flow_us"] - base, 2)
+    out["multi_minus_parent_us"] = round(out["multi_us"] - base, 2)
+    for h in pctx:
+        P.fws_gpu_ctx_destroy(h)
+    ctx.close()
+    return out
+
+
+def flow_frames(n, frame_bytes, read_bytes, rounds):
+    """--flow (ii): n connections each receive one BIN frame of frame_bytes on
+    the wire (header included) in reads of read_bytes. The flow protocol uploads
+    every read once and makes one launch per step for all connections; the
+    alternative today keeps the unfinished frame on the host and, per read and
+    connection, uploads the buffer so far and runs the carry call on it
+    (MessageStream's protocol). Pinned host memory, uploads on the timed stream."""
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(5)
+    steps = frame_bytes // read_bytes
+    assert steps * read_bytes == frame_bytes and read_bytes % 16 == 0 and read_bytes <= _lib.FWS_MSG_MULTI_MAX_READ
+    body = frame_bytes - 14
+    streams = []
+    for c in range(n):
+        key = int(rng.integers(0, 1 << 32))
+        streams.append(np.concatenate([np.frombuffer(header(2, 1, body, key), dtype=np.uint8),
+                                       rng.integers(0, 256, body, dtype=np.uint8)]))
+    host = torch.from_numpy(np.stack(streams)).pin_memory()              # [n, frame_bytes]
+    by_step = torch.from_numpy(np.stack(streams).reshape(n, steps, read_bytes).transpose(1, 0, 2).copy()).pin_memory()
+    u8 = dict(dtype=torch.uint8, device=dev)
+    cap = 8
+    # flow: one slot per connection
+    wire, dst, ctl = torch.zeros(n * read_bytes, **u8), torch.zeros(n * read_bytes, **u8), torch.zeros(n * 64, **u8)
+    frames, msgs = torch.zeros(n * cap * 24, **u8), torch.zeros(n * cap * 32, **u8)
+    res, mres = torch.zeros(n * 40, **u8), torch.zeros(n * 64, **u8)
+    flows = torch.zeros(n * _lib.MSG_FLOW.itemsize, **u8)
+    desc = np.zeros(n, dtype=_lib.MSG_READ)
+    for r in range(n):
+        desc[r] = (r * read_bytes, r * read_bytes, r * 64, read_bytes, r, read_bytes, 64, r * cap, cap, r * cap, cap, 0)
+    reads = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    whole = torch.zeros(n * frame_bytes, **u8)        # the parts as a caller would keep them
+    # carry: one growing buffer
+    cwire, cdst, cctl = torch.zeros(frame_bytes, **u8), torch.zeros(frame_bytes, **u8), torch.zeros(64, **u8)
+    cfr, cms = torch.zeros(cap * 24, **u8), torch.zeros(cap * 32, **u8)
+    cres, cmres, carries = torch.zeros(40, **u8), torch.zeros(64, **u8), torch.zeros(n * 64, **u8)
+    ctx = gpu.Ctx(0, max_frames=cap, max_stream_bytes=frame_bytes)
+
+    def flow_pass(keep=False):
+        flows.zero_()
+        for k in range(steps):
+            wire.copy_(by_step[k].reshape(-1), non_blocking=True)
+            assert gpu.decode_messages_flow(ctx, wire, reads, n, read_bytes, frames, msgs, dst, ctl, res, mres, flows,
+                                            n) == 0
+            if keep:
+                whole.view(n, steps, read_bytes)[:, k].copy_(dst.view(n, read_bytes))
+
+    def carry_pass(keep=None):
+        carries.zero_()
+        for k in range(steps):
+            for c in range(n):
+                m = (k + 1) * read_bytes
+                cwire[:m].copy_(host[c, :m], non_blocking=True)
+                rc = gpu.decode_messages_carry(ctx, cwire, cap, cap, cdst, cctl, carries[c * 64:(c + 1) * 64],
+                                               frames=cfr, msgs=cms, result=cres, msg_result=cmres, n=m)[0]
+                assert rc == 0
+                if keep is not None and c == keep and k == steps - 1:
+                    torch.cuda.synchronize()
+                    return cdst[:body].clone(), gpu.read_msg_result(cmres)
+
+    # checked first: the flow parts joined are the carry call's message
+    flow_pass(keep=True)
+    torch.cuda.synchronize()
+    m = np.frombuffer(mres.cpu().numpy().tobytes(), dtype=_lib.MSG_RESULT)
+    assert (m["status"] == 0).all() and (m["n_msgs"] == 1).all() and (m["open_opcode"] == 0).all()
+    for c in (0, n - 1):
+        want, r = carry_pass(keep=c)
+        assert int(r["status"]) == 0 and int(r["n_msgs"]) == 1 and int(r["data_bytes"]) == body
+        # (the flow parts: 14 bytes fewer in the first read, every later read whole)
+        got = torch.cat([whole.view(n, steps, read_bytes)[c, 0, :read_bytes - 14],
+                         whole.view(n, steps, read_bytes)[c, 1:].reshape(-1)])
+        assert torch.equal(got, want), c
+    passes = {"flow": flow_pass, "carry_growing": carry_pass}
+    times = {k: [] for k in passes}
+    for rnd in range(rounds + 1):                     # (round 0 warms up)
+        for k in (list(passes) if rnd % 2 == 0 else list(passes)[::-1]):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            passes[k]()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd:
+                times[k].append(e0.elapsed_time(e1) * 1e3)
+    out = {"measure": "flow_frames", "n": n, "frame_bytes": frame_bytes, "read_bytes": read_bytes, "steps": steps,
+           "rounds": rounds, "device": torch.cuda.get_device_name(0),
+           "flow_calls": steps, "carry_calls": steps * n,
+           "flow_uploaded_per_conn": frame_bytes,
+           "carry_uploaded_per_conn": read_bytes * steps * (steps + 1) // 2}
+    for k in passes:
+        out[k + "_total_us"] = round(statistics.median(times[k]), 1)
+        out[k + "_total_us_min_max"] = [round(min(times[k]), 1), round(max(times[k]), 1)]
+    out["carry_over_flow"] = round(out["carry_growing_total_us"] / out["flow_total_us"], 2)
+    ctx.close()
+    return out
+
+
 def c3_stream(target):
     wire, descs, _ = gpu.config_c3(target=target)
     regions = np.zeros(len(descs), dtype=_lib.FRAME_DESC)
@@ -510,9 +699,26 @@ def main():
     ap.add_argument("--multi", action="store_true", help="measure fws_gpu_decode_messages_multi (see above)")
     ap.add_argument("--grid-n", default="1,8,64,512,4096", help="--multi: connections")
     ap.add_argument("--grid-kib", default="1,4,16,64", help="--multi: read sizes, KiB")
+    ap.add_argument("--flow", action="store_true", help="measure fws_gpu_decode_messages_flow (see above)")
+    ap.add_argument("--flow-conns", type=int, default=64, help="--flow (ii): connections")
+    ap.add_argument("--flow-frame-kib", type=int, default=1024, help="--flow (ii): a frame on the wire, KiB")
+    ap.add_argument("--flow-read-kib", type=int, default=16, help="--flow (ii): a read, KiB")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.flow:
+        if a.parent_lib:
+            grid_n = "1,64,512" if a.grid_n == ap.get_default("grid_n") else a.grid_n
+            for kib in map(int, a.grid_kib.split(",")):
+                for n in map(int, grid_n.split(",")):
+                    lines.append(json.dumps(flow_cost(n, kib << 10, os.path.abspath(a.parent_lib), a.rounds, a.steps)))
+                    print(lines[-1], flush=True)
+        lines.append(json.dumps(flow_frames(a.flow_conns, a.flow_frame_kib << 10, a.flow_read_kib << 10, a.rounds)))
+        print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.multi:
         for kib in map(int, a.grid_kib.split(",")):
             for n in map(int, a.grid_n.split(",")):
