@@ -76,6 +76,23 @@ RX_EVENT = np.dtype([("kind", "<u4"), ("opcode", "<u4"), ("is_ctl", "u1"), ("fra
 TX_DESC = np.dtype([("src_off", "<u8"), ("len", "<u8"), ("key", "<u4"), ("opcode", "u1"), ("fin", "u1"),
                     ("masked", "u1"), ("pad", "u1")])
 assert FRAME_DESC.itemsize == 24 and FRAME_INFO.itemsize == 24 and TX_DESC.itemsize == 24
+# fws_gpu_encode_messages_multi: a send's limits, the fragment key, the connection's state, the send and its result
+FWS_TX_MULTI_MAX_SEND = 128 << 10
+FWS_TX_MULTI_MAX_FRAMES = 256
+
+
+def FWS_TX_FRAG_KEY(key, j):
+    return (key + j * 0x9E3779B9) & 0xFFFFFFFF
+
+
+TX_CONN = np.dtype([("last_msg_not_fin", "<u4"), ("reserved0", "<u4"), ("frames", "<u8"), ("wire_bytes", "<u8"),
+                    ("reserved", "<u8")])
+TX_SEND = np.dtype([("src_off", "<u8"), ("out_off", "<u8"), ("len", "<u4"), ("out_cap", "<u4"), ("conn", "<u4"),
+                    ("max_frame", "<u4"), ("key", "<u4"), ("frame_type", "u1"), ("last", "u1"), ("masked", "u1"),
+                    ("pad", "u1"), ("frame_base", "<u4"), ("frame_cap", "<u4"), ("reserved", "<u8", (2,))])
+TX_RESULT = np.dtype([("status", "<i4"), ("n_frames", "<u4"), ("out_len", "<u8"), ("last_msg_not_fin", "<u4"),
+                      ("pad", "<u4"), ("reserved", "<u8")])
+assert TX_CONN.itemsize == 32 and TX_SEND.itemsize == 64 and TX_RESULT.itemsize == 32
 assert DECODE_RESULT.itemsize == 40 and RX_EVENT.itemsize == 48
 RX_READ = np.dtype([("conn", "<u4"), ("flags", "<u4"), ("buf", "<u8"), ("size", "<u8"), ("capacity", "<u8")])
 RX_READ_RESULT = np.dtype([("ret", "<i4"), ("pad", "<u4"), ("events", "<u8"), ("n_events", "<u8"),
@@ -144,6 +161,7 @@ SIGNATURES = [
     ("fws_gen_batch", _I, [C.POINTER(GenParams), _P, _U64, _PU64, _P, _U64, _PU64, _P]),
     ("fws_tx_next", None, [_U32, _I, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("fws_gpu_encode_frames", _I, [_P, _P, _U64, _P, _P, _U32, _P, _P]),
+    ("fws_gpu_encode_messages_multi", _I, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _P]),
     ("fws_tx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_tx_session_destroy", None, [_P]),
     ("fws_tx_session_send", _I, [_P, _P, _P, _P, _P, _P, _U32, _P, _U64, _PU64]),

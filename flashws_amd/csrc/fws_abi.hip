@@ -499,6 +499,20 @@ int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire, const f
                                n_conns, (hipStream_t)stream);
 }
 
+int fws_gpu_encode_messages_multi(fws_gpu_ctx *ctx, void *dev_out, const void *dev_src, const fws_tx_send *dev_sends,
+                                  uint32_t n, uint32_t max_len, fws_frame_info *dev_frames,
+                                  fws_tx_result *dev_results, fws_tx_conn *dev_conns, uint32_t n_conns,
+                                  void *stream) {
+    if (n == 0) return 0;
+    // (dev_frames may be null: a send with frame_cap 0 writes no record)
+    if (!ctx || !dev_out || !dev_src || !dev_sends || !dev_results || !dev_conns) return FWS_ERR_INVALID;
+    if (((uintptr_t)dev_out & 15u) != 0) return FWS_ERR_INVALID;
+    if (max_len < 1u || max_len > FWS_TX_MULTI_MAX_SEND) return FWS_ERR_INVALID;
+    if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
+    return fws_launch_tx_multi((uint8_t *)dev_out, (const uint8_t *)dev_src, dev_sends, n, max_len, dev_frames,
+                               dev_results, dev_conns, n_conns, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 int fws_decode_prepare(fws_gpu_ctx *ctx, uint64_t len, uint32_t cap, bool utf8) {

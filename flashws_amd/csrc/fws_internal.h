@@ -344,6 +344,10 @@ int fws_launch_msg_flow(const uint8_t *wire, const fws_msg_read *reads, uint32_t
                         fws_frame_info *frames, fws_msg_info *msgs, uint8_t *dst, uint8_t *ctl,
                         fws_decode_result *res, fws_msg_result *mres, fws_msg_flow *flows, uint32_t n_conns,
                         hipStream_t s);
+// fws_gpu_encode_messages_multi (tx_multi_kernels.hip): n sends, one workgroup each; no workspace
+int fws_launch_tx_multi(uint8_t *out, const uint8_t *src, const fws_tx_send *sends, uint32_t n, uint32_t max_len,
+                        fws_frame_info *frames, fws_tx_result *res, fws_tx_conn *conns, uint32_t n_conns,
+                        hipStream_t s);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
                        hipStream_t s, const uint32_t *deny = nullptr);

@@ -955,3 +955,120 @@ class TxState:
         op, fin = C.c_uint8(), C.c_uint8()
         lib().fws_tx_next(frame_type, int(last), C.byref(self.last_msg_not_fin), C.byref(op), C.byref(fin))
         return op.value, fin.value
+
+
+def encode_messages_multi(ctx, out, src, sends, n, max_len, frames, results, conns, n_conns, stream=None):
+    """fws_gpu_encode_messages_multi: the sends of many connections cut into
+    frames and encoded in one launch. sends holds n fws_tx_send descriptors
+    (_lib.TX_SEND) in a device uint8 tensor, results n fws_tx_result
+    (_lib.TX_RESULT), conns n_conns fws_tx_conn states (_lib.TX_CONN, zeros for
+    new connections); frames (FRAME_INFO records) may be None when every
+    frame_cap is 0. Returns the call's status; nothing is synchronised."""
+    return lib().fws_gpu_encode_messages_multi(ctx.h, _ptr(out), _ptr(src), _ptr(sends), n, max_len,
+                                               _ptr(frames) if frames is not None else None, _ptr(results),
+                                               _ptr(conns), n_conns, _stream_handle(stream))
+
+
+def read_tx_conn(conns, conn=0):
+    sz = _lib.TX_CONN.itemsize
+    return np.frombuffer(conns[conn * sz:(conn + 1) * sz].cpu().numpy().tobytes(), dtype=_lib.TX_CONN)[0]
+
+
+class MessageSender:
+    """The send side of MessageFlow: send({conn: (frame_type, payload, last)})
+    makes one upload, one fws_gpu_encode_messages_multi call and one
+    synchronisation for all connections and returns {conn: wire bytes}. The
+    opcode / FIN sequencing state of every connection stays on the device
+    (self.conns). A payload over max_send is cut into pieces that are multiples
+    of max_frame and sent by successive calls inside the same send (each one
+    upload, one launch, one synchronisation), `last` on the final piece only;
+    piece i of a masked message starts its keys where piece i - 1 stopped
+    (FWS_TX_FRAG_KEY(key, frames before it)), so frame f of the message has
+    FWS_TX_FRAG_KEY(key, f). pieces[conn] = [(offset, length, key), ...] of the
+    last send; calls counts the launches."""
+
+    def __init__(self, ctx, n_conns, max_send, device="cuda:0"):
+        if not 1 <= max_send <= _lib.FWS_TX_MULTI_MAX_SEND:
+            raise ValueError("max_send must be 1..FWS_TX_MULTI_MAX_SEND")
+        self.ctx, self.n_conns, self.max_send = ctx, n_conns, max_send
+        self.src_slot = (max_send + 15) & ~15
+        self.out_slot = (max_send + 14 * _lib.FWS_TX_MULTI_MAX_FRAMES + 15) & ~15
+        self.dev = torch.device(device)
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        pin = dict(dtype=torch.uint8, pin_memory=True)
+        self._sizes = dict(src=self.src_slot, out=self.out_slot, sends=_lib.TX_SEND.itemsize,
+                           res=_lib.TX_RESULT.itemsize)
+        self._d = {k: torch.zeros(n_conns * sz, **u8) for k, sz in self._sizes.items()}
+        self._h = {k: torch.zeros(n_conns * sz, **pin) for k, sz in self._sizes.items()}
+        self.conns = torch.zeros(n_conns * _lib.TX_CONN.itemsize, **u8)
+        self.calls = 0
+        self.pieces = {}
+
+    def _call(self, work, max_frame, masked):
+        """One launch for {conn: (frame_type, piece, last, key)}: the wire bytes per connection."""
+        conns, n = list(work), len(work)
+        sz, hs = self._sizes, self._h["src"].numpy()
+        desc = np.zeros(n, dtype=_lib.TX_SEND)
+        for i, c in enumerate(conns):
+            ft, piece, last, key = work[c]
+            hs[i * self.src_slot:i * self.src_slot + len(piece)] = np.frombuffer(piece, dtype=np.uint8)
+            d = desc[i]
+            d["src_off"], d["out_off"], d["len"], d["out_cap"] = i * self.src_slot, i * self.out_slot, len(piece), \
+                self.out_slot
+            d["conn"], d["max_frame"], d["key"], d["frame_type"] = c, max_frame, key, ft
+            d["last"], d["masked"] = int(bool(last)), int(bool(masked))
+        self._h["sends"].numpy()[:n * sz["sends"]] = desc.view(np.uint8)
+        stream = torch.cuda.current_stream(self.dev)
+        for k in ("src", "sends"):
+            self._d[k][:n * sz[k]].copy_(self._h[k][:n * sz[k]], non_blocking=True)
+        max_len = max(1, max(len(w[1]) for w in work.values()))
+        d = self._d
+        check("fws_gpu_encode_messages_multi",
+              encode_messages_multi(self.ctx, d["out"], d["src"], d["sends"], n, max_len, None, d["res"], self.conns,
+                                    self.n_conns, stream=stream))
+        self.calls += 1
+        for k in ("res", "out"):
+            self._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
+        stream.synchronize()
+        res = np.frombuffer(self._h["res"].numpy()[:n * sz["res"]].tobytes(), dtype=_lib.TX_RESULT)
+        out = {}
+        for i, c in enumerate(conns):
+            if int(res[i]["status"]):
+                raise FwsError(f"fws_gpu_encode_messages_multi refused the send of connection {c}",
+                               int(res[i]["status"]))
+            o = i * self.out_slot
+            out[c] = self._h["out"].numpy()[o:o + int(res[i]["out_len"])].tobytes()
+        return out
+
+    def send(self, sends, max_frame=0, keys=None, masked=True):
+        step = self.max_send
+        if max_frame:
+            step = min(self.max_send // max_frame, _lib.FWS_TX_MULTI_MAX_FRAMES) * max_frame
+        queue, self.pieces = {}, {}
+        for conn, (ft, payload, last) in sends.items():
+            if not 0 <= conn < self.n_conns:
+                raise ValueError(f"connection {conn} out of range")
+            payload = bytes(payload)
+            if keys is not None:
+                key = keys[conn] & 0xFFFFFFFF
+            else:
+                key = int(np.random.randint(0, 1 << 32, dtype=np.uint64)) if masked else 0
+            control = bool(ft & 8)
+            if control or len(payload) <= (step if max_frame else self.max_send):
+                cuts = [(0, len(payload))]
+            elif not max_frame or step == 0:
+                raise ValueError(f"a send of {len(payload)} bytes exceeds max_send = {self.max_send} and "
+                                 f"max_frame = {max_frame} gives no piece size")
+            else:
+                cuts = [(o, min(step, len(payload) - o)) for o in range(0, len(payload), step)]
+            per = step // max_frame if max_frame else 0
+            self.pieces[conn] = [(o, ln, _lib.FWS_TX_FRAG_KEY(key, i * per)) for i, (o, ln) in enumerate(cuts)]
+            queue[conn] = [(ft, payload[o:o + ln], bool(last) and i + 1 == len(cuts), k)
+                           for i, (o, ln, k) in enumerate(self.pieces[conn])]
+        out = {c: b"" for c in sends}
+        while queue:
+            work = {c: q.pop(0) for c, q in queue.items()}
+            for c, b in self._call(work, max_frame, masked).items():
+                out[c] += b
+            queue = {c: q for c, q in queue.items() if q}
+        return out

@@ -680,6 +680,114 @@ void fws_tx_next(uint32_t frame_type, int last_frame_if_possible, uint8_t *last_
 int fws_gpu_encode_frames(fws_gpu_ctx *ctx, void *dev_out, uint64_t out_cap, const void *dev_src,
                           const fws_tx_desc *dev_descs, uint32_t n, uint64_t *dev_out_len, void *stream);
 
+/* ---- the sends of many connections encoded in one launch --------------------
+ * The TX counterpart of fws_gpu_decode_messages_multi: n sends, one workgroup
+ * per send, each into its own region of dev_out. A send is one payload; the
+ * device cuts it into frames of max_frame payload bytes and takes opcode and FIN
+ * from the connection's state in device memory (SendFrame's rule, fws_tx_next),
+ * which it reads and rewrites, so replies need no host round trip and no
+ * per-frame descriptor. */
+#define FWS_TX_MULTI_MAX_SEND   (128u << 10)   /* payload bytes of one send */
+#define FWS_TX_MULTI_MAX_FRAMES 256u           /* frames one send may be cut into */
+/* key of a masked send's fragment j (j = 0: the send's key) */
+#define FWS_TX_FRAG_KEY(key, j) ((uint32_t)((key) + (uint32_t)(j) * 0x9E3779B9u))
+
+typedef struct fws_tx_conn {        /* device memory; all zero = a new connection */
+    uint32_t last_msg_not_fin;      /* SendFrame's last_msg_not_fin_ (fws_tx_next) */
+    uint32_t reserved0;             /* 0 */
+    uint64_t frames;                /* running count of frames written */
+    uint64_t wire_bytes;            /* running sum of out_len */
+    uint64_t reserved;              /* 0 */
+} fws_tx_conn;                      /* 32 bytes */
+
+typedef struct fws_tx_send {        /* device memory, one per send */
+    uint64_t src_off;               /* payload at dev_src + src_off, any alignment */
+    uint64_t out_off;               /* its region of dev_out, 16-B aligned */
+    uint32_t len;                   /* payload bytes (0 allowed) */
+    uint32_t out_cap;               /* bytes of the region */
+    uint32_t conn;                  /* index into dev_conns, < n_conns; distinct within a call */
+    uint32_t max_frame;             /* data sends: payload bytes per frame; 0 = one frame */
+    uint32_t key;                   /* masked sends */
+    uint8_t  frame_type;            /* WSTxFrameType: 1 TEXT, 2 BIN, 8 CLOSE, 9 PING, 10 PONG */
+    uint8_t  last;                  /* last_frame_if_possible of the send's last frame */
+    uint8_t  masked;                /* 1 client frames, 0 server frames */
+    uint8_t  pad;                   /* 0 */
+    uint32_t frame_base, frame_cap; /* its slice of dev_frames (frame_cap 0: no records) */
+    uint64_t reserved[2];           /* 0 */
+} fws_tx_send;                      /* 64 bytes */
+
+typedef struct fws_tx_result {
+    int32_t  status;
+    uint32_t n_frames;              /* frames of the send, also past frame_cap */
+    uint64_t out_len;               /* bytes written; on FWS_ERR_CAPACITY the bytes needed */
+    uint32_t last_msg_not_fin;      /* the connection's state after the send */
+    uint32_t pad;
+    uint64_t reserved;
+} fws_tx_result;                    /* 32 bytes */
+
+/* Per send s (offsets relative to the send's region, dev_out + out_off):
+ *   frames    a control send (frame_type & 8) is one frame, max_frame ignored. A
+ *             data send with max_frame == 0 or len <= max_frame is one frame
+ *             (len == 0: one empty frame). Otherwise k = ceil(len / max_frame)
+ *             frames, the first k - 1 of max_frame payload bytes, the last of
+ *             the rest. Frame j's opcode and FIN are what
+ *             fws_tx_next(frame_type, j == k - 1 ? last : 0, &state, ...) gives
+ *             for frames 0 .. k - 1 in order from dev_conns[conn].last_msg_not_fin:
+ *             exactly k SendFrame calls. A control send neither uses nor changes
+ *             the state; its FIN is `last`.
+ *   bytes     the frames back to back from the region's start, each what
+ *             fws_gpu_encode_frames writes for the same payload slice, opcode,
+ *             FIN, mask bit and key; frame j of a masked send uses
+ *             FWS_TX_FRAG_KEY(key, j), XORed from phase 0. No byte outside
+ *             [out_off, out_off + out_len) is written, inside out_cap or not (a
+ *             tail of out_len % 16 bytes is stored partially). Regions of
+ *             different sends must not overlap.
+ *   state     on success dev_conns[conn] gets the new last_msg_not_fin,
+ *             frames += n_frames, wire_bytes += out_len; the result echoes the new
+ *             last_msg_not_fin.
+ *   records   dev_frames[frame_base + j], j < min(n_frames, frame_cap): hdr_off
+ *             (relative to the region), payload_len, key (0 when unmasked), the
+ *             wire opcode, fin, hdr_len, flags = 0 -- for a masked send the
+ *             records fws_gpu_decode_messages_flow reports for the same bytes.
+ *             frame_cap < n_frames is not an error. dev_frames may be NULL when
+ *             every frame_cap is 0: the kernel then never dereferences it.
+ *   refusals  per send; the call still returns 0 and other sends are untouched.
+ *             Nothing is written to the region, the records or the state, and
+ *             the result's other fields are zero except where stated. Tested in
+ *             this order:
+ *               FWS_ERR_INVALID        out_off not 16-B aligned, conn >= n_conns,
+ *                                      frame_type not 1, 2, 8, 9 or 10
+ *               FWS_ERR_CONTROL_FRAME  a control send with len > 125
+ *               FWS_ERR_DECLINED       len > max_len, len > FWS_TX_MULTI_MAX_SEND
+ *                                      or more than FWS_TX_MULTI_MAX_FRAMES frames:
+ *                                      split the send, or use fws_gpu_encode_frames
+ *               FWS_ERR_CAPACITY       the bytes needed exceed out_cap; out_len =
+ *                                      the bytes needed, n_frames is set (the
+ *                                      count is closed-form: known before the
+ *                                      first store)
+ *             Two sends of one call that name the same conn are a contract
+ *             violation: the result is undefined for that connection only.
+ *   streaming a message over FWS_TX_MULTI_MAX_SEND goes as sends of at most that
+ *             size, each a multiple of max_frame, `last` on the final one only, in
+ *             successive calls on one stream: the state makes the pieces' frames
+ *             continuations. Each piece of a masked message restarts its keys at
+ *             its own `key` (the reference draws a fresh key per frame,
+ *             w_socket.h:860, so any key is as good).
+ *   max_len   the caller's upper bound on len, between 1 and
+ *             FWS_TX_MULTI_MAX_SEND. It selects the kernel form: up to 16 KiB a
+ *             workgroup of 256 threads, above one of 1024.
+ *   ordering  stream-ordered: no host synchronisation, no device-to-host copy, no
+ *             allocation, no workspace. Two calls queued on one stream chain
+ *             through dev_conns; a captured call needs no reset node.
+ * n == 0 returns 0 without a launch. Otherwise ctx and every pointer but
+ * dev_frames must be non-null, dev_out 16-B aligned and max_len in range, or the
+ * call returns FWS_ERR_INVALID before any device call. Out of scope: two sends
+ * of one connection in one call. */
+int fws_gpu_encode_messages_multi(fws_gpu_ctx *ctx, void *dev_out, const void *dev_src,
+                                  const fws_tx_send *dev_sends, uint32_t n, uint32_t max_len,
+                                  fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                  fws_tx_conn *dev_conns, uint32_t n_conns, void *stream);
+
 /* Host-memory send for one connection: WSocket::SendFrame (w_socket.h:832-944)
  * for its next n frames, in order. Frame i = payloads[i][0..lens[i]) of
  * WSTxFrameType frame_types[i] with last_frame_if_possible = last[i]; a client

@@ -52,10 +52,21 @@ after 64 distinct ones. One JSON line per grid point.
        Total stream time per pass, uploads included, and bytes uploaded per
        connection; the flow parts joined are checked against the carry call's
        message first.
+--tx-multi measures fws_gpu_encode_messages_multi: n
+connections x one masked send each of 1 / 4 / 16 / 64 KiB in one frame (n in 1,
+64, 512), and 64 x 64 KiB in frames of 4096 bytes. One multi call against what a
+caller does today with the same library -- n fws_gpu_encode_frames calls, one
+per connection into its own region, and one fws_gpu_encode_frames batch over
+all frames (one back-to-back output the host must take apart) -- and a
+device-to-device copy of the same bytes as a bandwidth reference; the forms
+alternate within each round, and every form's output is compared byte for byte
+first. max_len is the send size, so the small kernel form is the one measured
+up to 16 KiB. One JSON line per grid point.
 usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out FILE]
        python tools/msg_bench.py --carry [--parent-lib SO] [--read-mib M] [--target MiB] [--out FILE]
        python tools/msg_bench.py --multi [--grid-n N,N,..] [--grid-kib K,K,..] [--rounds R] [--out FILE]
-       python tools/msg_bench.py --flow [--parent-lib SO] [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]"""
+       python tools/msg_bench.py --flow [--parent-lib SO] [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
+       python tools/msg_bench.py --tx-multi [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -598,6 +609,101 @@ def flow_frames(n, frame_bytes, read_bytes, rounds):
     return out
 
 
+def tx_multi_bench(n, size, max_frame, rounds, steps):
+    """--tx-multi: n connections each send `size` bytes, masked, in frames of
+    max_frame bytes (0: one frame): one fws_gpu_encode_messages_multi call against
+    n fws_gpu_encode_frames calls (one per connection, into the same regions) and
+    one fws_gpu_encode_frames batch over all frames (one back-to-back output)."""
+    L = _lib.lib()
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(77 * n + size + max_frame)
+    cuts = [(o, min(max_frame, size - o)) for o in range(0, size, max_frame)] if max_frame else [(0, size)]
+    k = len(cuts)
+    hdr = [6 + (0 if ln < 126 else 2 if ln <= 65535 else 8) for _, ln in cuts]
+    need = size + sum(hdr)
+    slot = (need + 15) & ~15
+    keys = rng.integers(0, 1 << 32, n, dtype=np.uint64)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    src = torch.from_numpy(rng.integers(0, 256, n * size, dtype=np.uint8)).to(dev)
+    out_multi, out_seq = torch.zeros(n * slot, **u8), torch.zeros(n * slot, **u8)
+    out_batch, copy_dst = torch.zeros(n * need + 16, **u8), torch.zeros(n * slot, **u8)
+    sends = np.zeros(n, dtype=_lib.TX_SEND)
+    descs = np.zeros(n * k, dtype=_lib.TX_DESC)
+    for r in range(n):
+        s = sends[r]
+        s["src_off"], s["out_off"], s["len"], s["out_cap"], s["conn"], s["max_frame"] = r * size, r * slot, size, slot, \
+            r, max_frame
+        s["key"], s["frame_type"], s["last"], s["masked"] = keys[r], 2, 1, 1
+        for j, (o, ln) in enumerate(cuts):                # what a caller builds today: fws_tx_next per frame
+            descs[r * k + j] = (r * size + o, ln, _lib.FWS_TX_FRAG_KEY(int(keys[r]), j), 2 if j == 0 else 0,
+                                int(j == k - 1), 1, 0)
+    d_sends = torch.from_numpy(sends.view(np.uint8).copy()).to(dev)
+    d_descs = torch.from_numpy(descs.view(np.uint8).copy()).to(dev)
+    res = torch.zeros(n * _lib.TX_RESULT.itemsize, **u8)
+    conns = torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
+    lens = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    ctx = gpu.Ctx(0, max_frames=n * k + 64, max_stream_bytes=n * slot + 4096)
+    s = torch.cuda.current_stream()
+    enc = L.fws_gpu_encode_frames
+    p = dict(src=src.data_ptr(), out=out_seq.data_ptr(), descs=d_descs.data_ptr(), lens=lens.data_ptr())
+
+    def f_multi(i):
+        assert gpu.encode_messages_multi(ctx, out_multi, src, d_sends, n, size, None, res, conns, n) == 0
+
+    def forced(threads):                              # one kernel form whatever max_len says (tuning hook)
+        def f(i):
+            L.fws_internal_set_tx_multi_threads(threads)
+            f_multi(i)
+            L.fws_internal_set_tx_multi_threads(0)
+        return f
+
+    def f_seq(i):
+        h = s.cuda_stream
+        for r in range(n):
+            assert enc(ctx.h, p["out"] + r * slot, slot, p["src"], p["descs"] + r * k * 24, k, p["lens"] + 8 * r, h) == 0
+
+    def f_batch(i):
+        assert enc(ctx.h, out_batch.data_ptr(), n * need + 16, p["src"], p["descs"], n * k, p["lens"] + 8 * n,
+                   s.cuda_stream) == 0
+
+    def f_copy(i):
+        copy_dst.copy_(out_multi)
+
+    # checked first: every form writes the same frames
+    for f in (f_multi, f_seq, f_batch):
+        f(0)
+    torch.cuda.synchronize()
+    r_ = np.frombuffer(res.cpu().numpy().tobytes(), dtype=_lib.TX_RESULT)
+    assert (r_["status"] == 0).all() and (r_["out_len"] == need).all() and (r_["n_frames"] == k).all()
+    ln_ = lens.cpu().numpy()
+    assert (ln_[:n] == need).all() and ln_[n] == n * need
+    a = out_multi.view(n, slot)[:, :need]
+    assert torch.equal(a, out_seq.view(n, slot)[:, :need]), "the multi call and the per-connection calls differ"
+    assert torch.equal(a.reshape(-1), out_batch[:n * need]), "the multi call and the batch differ"
+    for threads in (256, 1024):                       # either form writes what the default one wrote
+        out_multi.zero_()
+        forced(threads)(0)
+        assert torch.equal(out_multi.view(n, slot)[:, :need], out_seq.view(n, slot)[:, :need]), threads
+    forms = {"multi": (f_multi, steps), "multi_256": (forced(256), steps), "multi_1024": (forced(1024), steps),
+             "seq": (f_seq, max(1, min(steps, 2048 // n))), "batch": (f_batch, steps), "copy": (f_copy, steps)}
+    times = {name: [] for name in forms}
+    for rnd in range(rounds):
+        for name in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[name].append(timed(forms[name][0], forms[name][1], warm=2 if name == "seq" else 10))
+    out = {"measure": "tx_multi", "n": n, "send_bytes": size, "max_frame": max_frame, "frames_per_send": k,
+           "form": "small" if size <= (16 << 10) else "full", "wire_bytes": n * need, "rounds": rounds,
+           "steps": {name: v[1] for name, v in forms.items()}, "device": torch.cuda.get_device_name(0)}
+    for name in forms:
+        out[name + "_us"] = round(statistics.median(times[name]), 2)
+        out[name + "_us_min_max"] = [round(min(times[name]), 2), round(max(times[name]), 2)]
+    out["seq_over_multi"] = round(out["seq_us"] / out["multi_us"], 2)
+    out["batch_over_multi"] = round(out["batch_us"] / out["multi_us"], 2)
+    out["multi_over_copy"] = round(out["multi_us"] / out["copy_us"], 2)
+    out["multi_wire_gb_s"] = round(n * need / out["multi_us"] / 1e3, 2)
+    ctx.close()
+    return out
+
+
 def c3_stream(target):
     wire, descs, _ = gpu.config_c3(target=target)
     regions = np.zeros(len(descs), dtype=_lib.FRAME_DESC)
@@ -703,9 +809,20 @@ def main():
     ap.add_argument("--flow-conns", type=int, default=64, help="--flow (ii): connections")
     ap.add_argument("--flow-frame-kib", type=int, default=1024, help="--flow (ii): a frame on the wire, KiB")
     ap.add_argument("--flow-read-kib", type=int, default=16, help="--flow (ii): a read, KiB")
+    ap.add_argument("--tx-multi", action="store_true", help="measure fws_gpu_encode_messages_multi (see above)")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.tx_multi:
+        grid_n = "1,64,512" if a.grid_n == ap.get_default("grid_n") else a.grid_n
+        points = [(n, kib << 10, 0) for kib in map(int, a.grid_kib.split(",")) for n in map(int, grid_n.split(","))]
+        for n, size, mf in points + [(64, 64 << 10, 4096)]:
+            lines.append(json.dumps(tx_multi_bench(n, size, mf, a.rounds, a.steps)))
+            print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.flow:
         if a.parent_lib:
             grid_n = "1,64,512" if a.grid_n == ap.get_default("grid_n") else a.grid_n
