@@ -93,6 +93,13 @@ TX_SEND = np.dtype([("src_off", "<u8"), ("out_off", "<u8"), ("len", "<u4"), ("ou
 TX_RESULT = np.dtype([("status", "<i4"), ("n_frames", "<u4"), ("out_len", "<u8"), ("last_msg_not_fin", "<u4"),
                       ("pad", "<u4"), ("reserved", "<u8")])
 assert TX_CONN.itemsize == 32 and TX_SEND.itemsize == 64 and TX_RESULT.itemsize == 32
+# fws_gpu_reply_messages_multi: what is answered, the connection's reply state and a read's output region
+FWS_REPLY_CONTROL = 1   # PING -> PONG, CLOSE -> CLOSE
+FWS_REPLY_ECHO = 2      # every data part goes back as one frame
+REPLY_STATE = np.dtype([("close_sent", "<u4"), ("close_code", "<u4"), ("reserved", "<u8")])
+REPLY_REGION = np.dtype([("out_off", "<u8"), ("out_cap", "<u4"), ("frame_base", "<u4"), ("frame_cap", "<u4"),
+                         ("reserved0", "<u4"), ("reserved", "<u8")])
+assert REPLY_STATE.itemsize == 16 and REPLY_REGION.itemsize == 32
 assert DECODE_RESULT.itemsize == 40 and RX_EVENT.itemsize == 48
 RX_READ = np.dtype([("conn", "<u4"), ("flags", "<u4"), ("buf", "<u8"), ("size", "<u8"), ("capacity", "<u8")])
 RX_READ_RESULT = np.dtype([("ret", "<i4"), ("pad", "<u4"), ("events", "<u8"), ("n_events", "<u8"),
@@ -162,6 +169,8 @@ SIGNATURES = [
     ("fws_tx_next", None, [_U32, _I, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     ("fws_gpu_encode_frames", _I, [_P, _P, _U64, _P, _P, _U32, _P, _P]),
     ("fws_gpu_encode_messages_multi", _I, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _P]),
+    ("fws_gpu_reply_messages_multi", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _U32,
+                                          _P]),
     ("fws_tx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_tx_session_destroy", None, [_P]),
     ("fws_tx_session_send", _I, [_P, _P, _P, _P, _P, _P, _U32, _P, _U64, _PU64]),

@@ -348,6 +348,12 @@ int fws_launch_msg_flow(const uint8_t *wire, const fws_msg_read *reads, uint32_t
 int fws_launch_tx_multi(uint8_t *out, const uint8_t *src, const fws_tx_send *sends, uint32_t n, uint32_t max_len,
                         fws_frame_info *frames, fws_tx_result *res, fws_tx_conn *conns, uint32_t n_conns,
                         hipStream_t s);
+// fws_gpu_reply_messages_multi (reply_kernels.hip): the reply frames of n decoded reads, one workgroup each; no
+// workspace
+int fws_launch_reply(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
+                     const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
+                     const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames, fws_tx_result *res,
+                     fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns, uint32_t flags, hipStream_t s);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
                        hipStream_t s, const uint32_t *deny = nullptr);

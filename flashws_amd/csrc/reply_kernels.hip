@@ -1,0 +1,375 @@
+// reply_kernels.hip -- fws_gpu_reply_messages_multi: the reply frames of many
+// connections built from what a message decode wrote, in one launch, one
+// workgroup per read; the link between k_msg_flow / k_msg_multi and k_tx_multi.
+//
+// A read's items are its n_msgs entries, in order, then the open part: at most
+// FWS_MSG_MULTI_MAX_FRAMES + 2. An item gives one frame or none: a PING a PONG,
+// a CLOSE a CLOSE (FWS_REPLY_CONTROL, w_socket.h:661-710), a TEXT / BIN entry or
+// the open part a data frame (FWS_REPLY_ECHO); nothing follows the CLOSE.
+//
+// Sequencing. SendFrame's rule (fws_tx_next) over these items is serial in form
+// only: every entry ends its message, so after any data frame but the open part
+// no message is open, and the one frame whose opcode depends on the connection's
+// last_msg_not_fin is the first data frame of the read. So the walk is two
+// minima over the items, taken with LDS atomics -- the first CLOSE (items behind
+// it are dropped) and the first data item (a continuation when a message is
+// open) -- and each item's frame is decided by its own thread.
+//
+// Frame table. A workgroup scan of (frame?, H(len) + len) over the items gives
+// each frame its index and its offset; the frames go, compacted, into an LDS
+// table: source address, payload length, offset, b0 and header length. The
+// total is known after the scan, before the first store: a refused read
+// (invalid, capacity) writes its result and nothing else.
+//
+// Bytes: the region is written as 16-B chunks from its aligned start, a wave
+// taking one 4 KiB unit per round as in k_tx_multi. The frames are irregular, so
+// a chunk finds its frame by a binary search in the table's offsets. A chunk
+// inside one payload is two aligned source loads shifted by the source
+// misalignment; a chunk that meets a header or the region's end (a seam) ORs,
+// for every frame that meets it, the header from registers and the source
+// window, each selected on its byte range (tx_multi_common.h). The region's last
+// chunk is stored bytewise up to out_len: no byte outside
+// [out_off, out_off + out_len) is written.
+#include "fws_device.h"
+#include "fws_internal.h"
+#include "tx_multi_common.h"
+
+namespace fwsk {
+
+constexpr uint32_t kRpItems = FWS_MSG_MULTI_MAX_FRAMES + 2u;   // the entries (a lead's and one per header), the open part
+constexpr uint32_t kRpNone = 0xFFFFFFFFu;
+
+struct RpArgs {
+    uint8_t *out;
+    const uint8_t *dst;
+    const uint8_t *ctl;
+    const fws_msg_read *reads;
+    const fws_msg_info *msgs;
+    const fws_msg_result *mres;
+    const fws_reply_region *regions;
+    fws_frame_info *frames;
+    fws_tx_result *res;
+    fws_tx_conn *conns;
+    fws_reply_state *states;
+    uint32_t n_conns;
+    uint32_t flags;
+};
+
+// the frame table (compacted: frame j of the region)
+struct RpTable {
+    uint64_t src[kRpItems];        // address of the payload's first byte
+    uint32_t off[kRpItems];        // the header's offset in the region
+    uint32_t len[kRpItems];        // payload bytes
+    uint32_t bh[kRpItems];         // b0 | header bytes << 8
+};
+
+__device__ __forceinline__ TmFrame rp_frame(const RpTable &t, uint32_t j) {
+    TmFrame f;
+    f.O = t.off[j];
+    f.plen = t.len[j];
+    f.hlen = t.bh[j] >> 8;
+    f.b0 = t.bh[j] & 0xFFu;
+    f.P = f.O + f.hlen;
+    f.E = f.P + f.plen;
+    f.soff = 0u;
+    f.key = 0u;
+    return f;
+}
+
+// the frame holding region offset a (< total): the last one whose offset is <= a
+__device__ __forceinline__ uint32_t rp_frame_of(const RpTable &t, uint32_t nf, uint32_t a) {
+    uint32_t lo = 0u, hi = nf - 1u;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if (t.off[mid] <= a) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+// tm_seam_chunk over the table: every frame from j on that meets [a, a + 16)
+// gives its header bytes and its payload bytes; bytes at or past the total stay
+// zero. A source block that holds no byte of the frame's payload is replaced by
+// one that does (its bytes are never selected), so every load is in bounds.
+__device__ u32x4 rp_seam_chunk(const RpTable &t, uint32_t nf, uint32_t a, uint32_t j) {
+    u32x4 x{0u, 0u, 0u, 0u};
+    for (; j < nf; ++j) {
+        const TmFrame f = rp_frame(t, j);
+        if (f.O >= a + 16u) break;
+        const uint32_t ho = tm_rel(f.O, a), hp = tm_rel(f.P, a), he = tm_rel(f.E, a);
+        if (hp > ho) {                                 // -16 < a - O < 16: the header is 10 bytes at most
+            const int off = (int)a - (int)f.O;
+            if (off > -16 && off < 16) x = x | tm_and_sel(tm_bytes_at(tm_hdr_vec(f, false), off), ho, hp);
+        }
+        if (he > hp) {
+            const uintptr_t s0 = (uintptr_t)t.src[j], s1 = s0 + f.plen;
+            const uintptr_t sa = s0 + (uintptr_t)a - (uintptr_t)f.P;
+            const uintptr_t safe = s0 & ~uintptr_t(15);
+            uintptr_t b0 = sa & ~uintptr_t(15), b1 = b0 + 16u;
+            if (b0 + 16u <= s0 || b0 >= s1) b0 = safe;
+            if (b1 + 16u <= s0 || b1 >= s1) b1 = safe;
+            const u32x4 w = tm_shr_bytes(gload16<false>(b0), gload16<false>(b1), (uint32_t)(sa & 15u));
+            x = x | tm_and_sel(w, hp, he);
+        }
+    }
+    return x;
+}
+
+__device__ __forceinline__ void rp_result(const RpArgs &a, uint32_t r, int32_t status, uint32_t n_frames,
+                                          uint64_t out_len, uint32_t lmnf) {
+    fws_tx_result x{};
+    x.status = status;
+    x.n_frames = n_frames;
+    x.out_len = out_len;
+    x.last_msg_not_fin = lmnf;
+    gput(a.res + r, x);
+}
+
+template <uint32_t kThreads>
+__global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
+    constexpr uint32_t kIpt = (kRpItems + kThreads - 1u) / kThreads;   // items per thread, consecutive
+    constexpr uint32_t kWaves = kThreads / 64u;
+    __shared__ RpTable s_t;
+    __shared__ uint32_t s_first_close, s_first_data, s_bad, s_open_item, s_close_code;
+    __shared__ uint32_t s_wc[kWaves], s_wb[kWaves];
+
+    const uint32_t tid = threadIdx.x, rd = blockIdx.x;
+    const fws_msg_read d = a.reads[rd];                // (uniform addresses: scalar loads)
+    const fws_msg_result mr = a.mres[rd];
+    const fws_reply_region g = a.regions[rd];
+    // Every field used below, in scalar registers here. Left alone the compiler loads a field where it is
+    // first used, behind the early exits, one dependent round trip after another (six before the entries'
+    // loads, some as vector loads); this empty statement makes them one batch of scalar loads and one wait.
+#ifndef FWS_REPLY_NO_HOIST                                // (A/B: make exp EXP_TAG=nohoist EXP_DEFS=-DFWS_REPLY_NO_HOIST)
+    asm volatile("" ::"s"(d.dst_off), "s"(d.ctl_off), "s"(d.conn), "s"(d.dst_cap), "s"(d.ctl_cap), "s"(d.msg_base),
+                 "s"(d.msg_cap), "s"(mr.status), "s"(mr.n_msgs), "s"(mr.open_opcode), "s"(mr.data_bytes),
+                 "s"(mr.ctl_bytes), "s"(mr.open_off), "s"(mr.open_len), "s"(g.out_off), "s"(g.out_cap),
+                 "s"(g.frame_base), "s"(g.frame_cap));
+#endif
+
+    // ---- what the descriptors alone decide
+    if ((g.out_off & 15u) || d.conn >= a.n_conns) {
+        if (tid == 0) rp_result(a, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
+        return;
+    }
+    fws_tx_conn *const conn = a.conns + d.conn;
+    fws_reply_state *const state = a.states + d.conn;
+    const bool undelivered = mr.status == FWS_ERR_DECLINED || mr.status == FWS_ERR_INVALID ||
+                             mr.n_msgs > d.msg_cap || mr.data_bytes > d.dst_cap || mr.ctl_bytes > d.ctl_cap;
+    if (!undelivered && mr.n_msgs > FWS_MSG_MULTI_MAX_FRAMES + 1u) {   // not a decode output
+        if (tid == 0) rp_result(a, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
+        return;
+    }
+    if (undelivered) {                                 // nothing to answer
+        if (tid == 0) rp_result(a, rd, 0, 0u, 0u, conn->last_msg_not_fin != 0u ? 1u : 0u);
+        return;
+    }
+
+    // ---- the items: each thread classifies its own
+    // The loads first, so that they are in flight together: every thread's entries, then both states. (The
+    // states are read by every wave before thread 0 rewrites them behind the barriers below. Tested where they
+    // are loaded, close_sent put the entries' loads, and behind them the payloads', one memory latency later.)
+    fws_msg_info e[kIpt];
+#pragma unroll
+    for (uint32_t k = 0; k < kIpt; ++k) {
+        e[k] = fws_msg_info{};
+        if (tid * kIpt + k < mr.n_msgs) e[k] = a.msgs[d.msg_base + tid * kIpt + k];
+    }
+    const uint32_t open = conn->last_msg_not_fin != 0u ? 1u : 0u;
+    const uint32_t close_sent = state->close_sent;
+    if (tid == 0) {
+        s_first_close = kRpNone;
+        s_first_data = kRpNone;
+        s_bad = 0u;
+        s_open_item = 0u;
+        s_close_code = 0u;
+    }
+    __syncthreads();
+    const bool control = (a.flags & FWS_REPLY_CONTROL) != 0u, echo = (a.flags & FWS_REPLY_ECHO) != 0u;
+    const uint8_t *const dsp = a.dst + d.dst_off, *const csp = a.ctl + d.ctl_off;
+    uint32_t kind[kIpt], len[kIpt], op[kIpt];          // kind: 0 no frame, 1 PONG, 2 CLOSE, 3 data entry, 4 the open part
+    uint64_t src[kIpt];
+#pragma unroll
+    for (uint32_t k = 0; k < kIpt; ++k) {
+        const uint32_t i = tid * kIpt + k;
+        kind[k] = 0u, len[k] = 0u, op[k] = 0u, src[k] = 0u;
+        uint64_t ln = 0u;
+        if (i < mr.n_msgs) {
+            ln = e[k].len;
+            op[k] = e[k].opcode;
+            if (control && (op[k] == 9u || op[k] == 8u)) {
+                kind[k] = op[k] == 9u ? 1u : 2u;
+                op[k] = op[k] == 9u ? 10u : 8u;
+                src[k] = (uint64_t)(uintptr_t)(csp + e[k].off);
+                if (ln > 125u) kind[k] = 0u, atomicOr(&s_bad, 1u);
+                else if (kind[k] == 2u) atomicMin(&s_first_close, i);
+            } else if (echo && (op[k] == 1u || op[k] == 2u)) {
+                kind[k] = 3u;
+                src[k] = (uint64_t)(uintptr_t)(dsp + e[k].off);
+            }
+        } else if (i == mr.n_msgs && echo && mr.open_opcode != 0u && mr.open_len > 0u) {
+            kind[k] = 4u;
+            ln = mr.open_len;
+            op[k] = mr.open_opcode;
+            src[k] = (uint64_t)(uintptr_t)(dsp + mr.open_off);
+            s_open_item = 1u;
+            if (op[k] != 1u && op[k] != 2u) kind[k] = 0u, atomicOr(&s_bad, 1u);
+        }
+        if (kind[k] >= 3u) {
+            if (ln > FWS_MSG_MULTI_MAX_READ) kind[k] = 0u, atomicOr(&s_bad, 1u);   // a read holds no more
+            else atomicMin(&s_first_data, i);
+        }
+        len[k] = (uint32_t)ln;
+    }
+    __syncthreads();
+    if (close_sent != 0u) {                            // nothing more to say
+        if (tid == 0) rp_result(a, rd, 0, 0u, 0u, open);
+        return;
+    }
+    if (s_bad) {                                       // not a decode output
+        if (tid == 0) rp_result(a, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
+        return;
+    }
+    const uint32_t fc = s_first_close, fd = s_first_data;
+
+    // ---- frame index and offset: a workgroup scan of (frame?, bytes)
+    uint32_t cnt = 0u, byt = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < kIpt; ++k) {
+        if (tid * kIpt + k > fc) kind[k] = 0u;         // behind the CLOSE
+        if (kind[k]) cnt += 1u, byt += tm_hdr_len(len[k], false) + len[k];
+    }
+    const uint32_t lane = tid & 63u, wv = tid >> 6;
+    uint32_t ic = cnt, ib = byt;                       // inclusive over the wave
+#pragma unroll
+    for (uint32_t s = 1u; s < 64u; s <<= 1) {
+        const uint32_t c2 = __shfl_up(ic, s), b2 = __shfl_up(ib, s);
+        if (lane >= s) ic += c2, ib += b2;
+    }
+    if (lane == 63u) s_wc[wv] = ic, s_wb[wv] = ib;
+    __syncthreads();
+    uint32_t pc = ic - cnt, pb = ib - byt, nf = 0u, total = 0u;
+#pragma unroll
+    for (uint32_t w = 0; w < kWaves; ++w) {
+        if (w < wv) pc += s_wc[w], pb += s_wb[w];
+        nf += s_wc[w], total += s_wb[w];               // <= 258 * (128 KiB + 10)
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kIpt; ++k) {
+        if (!kind[k]) continue;
+        const uint32_t i = tid * kIpt + k, hl = tm_hdr_len(len[k], false);
+        // fws_tx_next: a data frame that continues an unfinished message is a continuation; FIN but on the open part
+        const uint32_t b0 = kind[k] >= 3u ? ((kind[k] == 3u ? 0x80u : 0u) | ((i == fd && open) ? 0u : op[k])) : (0x80u | op[k]);
+        s_t.src[pc] = src[k];
+        s_t.off[pc] = pb;
+        s_t.len[pc] = len[k];
+        s_t.bh[pc] = b0 | (hl << 8);
+        if (kind[k] == 2u)                             // w_socket.h:668-673
+            s_close_code = len[k] >= 2u ? ((uint32_t)gget((const uint8_t *)(uintptr_t)src[k]) << 8) |
+                                              gget((const uint8_t *)(uintptr_t)src[k] + 1) : 1005u;
+        pc += 1u, pb += hl + len[k];
+    }
+    __syncthreads();
+
+    // ---- the verdict on the region
+    if (total > g.out_cap) {
+        if (tid == 0) rp_result(a, rd, FWS_ERR_CAPACITY, nf, total, 0u);
+        return;
+    }
+
+    // ---- the bytes (k_tx_multi's mapping: a wave's round is one 4 KiB unit, lane chunks 1 KiB apart)
+    uint8_t *const R = a.out + g.out_off;
+    const uint32_t nch = (total + 15u) >> 4;
+    const uint32_t lane0 = wv * (64u * kTmU) + lane;
+    for (uint32_t r0 = 0; r0 < nch; r0 += kThreads * kTmU) {   // (uniform trip count)
+        const uint32_t c0 = r0 + lane0;
+        uintptr_t sb[kTmU];
+        uint32_t sh[kTmU], fj[kTmU];
+        uint32_t full = 0, seam = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < kTmU; ++u) {
+            const uint32_t c = c0 + u * 64u, av = c < nch ? c * 16u : 0u;
+            const uint32_t j = nf > 1u ? rp_frame_of(s_t, nf, av) : 0u;
+            fj[u] = j;
+            const uint32_t P = s_t.off[j] + (s_t.bh[j] >> 8), E = P + s_t.len[j];
+            const bool in = c < nch && av >= P && av + 16u <= E;
+            if (in) full |= 1u << u;
+            else if (c < nch) seam |= 1u << u;
+            const uintptr_t sa = (uintptr_t)s_t.src[j] + (uintptr_t)(av - P);
+            sb[u] = sa & ~uintptr_t(15);
+            sh[u] = (uint32_t)(sa & 15u);
+        }
+        u32x4 v0[kTmU], v1[kTmU];
+#pragma unroll
+        for (uint32_t u = 0; u < kTmU; ++u) {
+            if ((full >> u) & 1u) {
+                v0[u] = gload16<false>(sb[u]);
+                v1[u] = gload16<false>(sh[u] ? sb[u] + 16u : sb[u]);
+            } else {
+                v0[u] = v1[u] = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kTmU; ++u)
+            if ((full >> u) & 1u)
+                gstore16<true>((uintptr_t)(R + (c0 + u * 64u) * 16u), tm_shr_bytes(v0[u], v1[u], sh[u]));
+        if (seam) {
+#pragma unroll
+            for (uint32_t u = 0; u < kTmU; ++u) {
+                if (!((seam >> u) & 1u)) continue;
+                const uint32_t av = (c0 + u * 64u) * 16u;
+                tm_store_chunk(R, av, total, rp_seam_chunk(s_t, nf, av, fj[u]));
+            }
+        }
+    }
+
+    // ---- the frame records
+    const uint32_t nrec = nf < g.frame_cap ? nf : g.frame_cap;
+    for (uint32_t j = tid; j < nrec; j += kThreads) {
+        const TmFrame f = rp_frame(s_t, j);
+        fws_frame_info fi;
+        fi.hdr_off = f.O;
+        fi.payload_len = f.plen;
+        fi.key = 0u;
+        fi.opcode = (uint8_t)(f.b0 & 15u);
+        fi.fin = (uint8_t)(f.b0 >> 7);
+        fi.hdr_len = (uint8_t)f.hlen;
+        fi.flags = 0;
+        gput(a.frames + g.frame_base + j, fi);
+    }
+
+    // ---- the result and both states, last
+    if (tid == 0) {
+        // the open part, when it is sent, is the last data frame and leaves its message open; any other ends one
+        const uint32_t next_open = fd < fc ? ((s_open_item && fc == kRpNone) ? 1u : 0u) : open;
+        rp_result(a, rd, 0, nf, total, next_open);
+        conn->last_msg_not_fin = next_open;
+        conn->frames += nf;
+        conn->wire_bytes += total;
+        if (fc != kRpNone) {
+            state->close_sent = 1u;
+            state->close_code = s_close_code;
+        }
+    }
+}
+
+}  // namespace fwsk
+
+using namespace fwsk;
+
+// Two forms by the decode call's max_len, as k_tx_multi: up to 16 KiB 256
+// threads, above 1024.
+constexpr uint32_t kRpSmallMax = 16u << 10;
+
+int fws_launch_reply(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
+                     const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
+                     const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames, fws_tx_result *res,
+                     fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns, uint32_t flags, hipStream_t s) {
+    static_assert(sizeof(fws_reply_state) == 16 && sizeof(fws_reply_region) == 32, "the ABI");
+    if (!n) return 0;
+    RpArgs a{out, dst, ctl, reads, msgs, mres, regions, frames, res, conns, states, n_conns, flags};
+    if (max_len <= kRpSmallMax)
+        hipLaunchKernelGGL((k_reply<256u>), dim3(n), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_reply<1024u>), dim3(n), dim3(1024), 0, s, a);
+    return fws_hip_status(hipGetLastError());
+}

@@ -498,6 +498,9 @@ class MessageFlow:
         self.status = [0] * n_conns
         self.calls = 0                                # fws_gpu_decode_messages_flow calls made
         self.uploaded = [0] * n_conns                 # wire bytes copied to the device, per connection
+        # MessageResponder's hooks: _queued(conns, max_len, stream) right after a call's launch, before its
+        # synchronisation; _synced(conns) right after it
+        self._queued = self._synced = None
 
     def _call(self, bufs):
         """One launch for {conn: bytes}: the units per connection; pending, parts and status updated."""
@@ -520,9 +523,13 @@ class MessageFlow:
               decode_messages_flow(self.ctx, d["wire"], d["reads"], n, max_len, d["frames"], d["msgs"], d["dst"],
                                    d["ctl"], d["res"], d["mres"], self.flows, self.n_conns, stream=stream))
         self.calls += 1
+        if self._queued:
+            self._queued(conns, max_len, stream)
         for k in ("mres", "msgs", "dst", "ctl"):
             self._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
         stream.synchronize()
+        if self._synced:
+            self._synced(conns)
         mres = np.frombuffer(self._h["mres"].numpy()[:n * sz["mres"]].tobytes(), dtype=MSG_RESULT)
         out = {}
         for i, c in enumerate(conns):
@@ -1072,3 +1079,86 @@ class MessageSender:
                 out[c] += b
             queue = {c: q for c, q in queue.items() if q}
         return out
+
+
+def reply_messages_multi(ctx, reads, n, max_len, msgs, dst, ctl, msg_results, regions, out, frames, results, conns,
+                         states, n_conns, flags, stream=None):
+    """fws_gpu_reply_messages_multi: the reply frames of n decoded reads in one
+    launch. reads, msgs, dst, ctl and msg_results are the tensors the decode
+    call (decode_messages_flow / decode_messages_multi) was given, max_len its
+    value; regions holds n fws_reply_region (_lib.REPLY_REGION), results n
+    fws_tx_result, conns n_conns fws_tx_conn (the array encode_messages_multi
+    takes), states n_conns fws_reply_state (_lib.REPLY_STATE, zeros for new
+    connections); frames may be None when every frame_cap is 0. flags:
+    _lib.FWS_REPLY_CONTROL | _lib.FWS_REPLY_ECHO. Returns the call's status;
+    nothing is synchronised."""
+    return lib().fws_gpu_reply_messages_multi(ctx.h, _ptr(reads), n, max_len, _ptr(msgs), _ptr(dst), _ptr(ctl),
+                                              _ptr(msg_results), _ptr(regions), _ptr(out),
+                                              _ptr(frames) if frames is not None else None, _ptr(results),
+                                              _ptr(conns), _ptr(states), n_conns, flags, _stream_handle(stream))
+
+
+def read_reply_state(states, conn=0):
+    sz = _lib.REPLY_STATE.itemsize
+    return np.frombuffer(states[conn * sz:(conn + 1) * sz].cpu().numpy().tobytes(), dtype=_lib.REPLY_STATE)[0]
+
+
+class MessageResponder:
+    """A MessageFlow that answers on the device: feed({conn: bytes}) returns
+    (units, replies), units exactly what flow.feed returns and replies[conn] the
+    connection's reply wire bytes -- PONGs and the CLOSE echo with
+    FWS_REPLY_CONTROL, every data part as a frame with FWS_REPLY_ECHO --
+    concatenated over the decode calls the feed made. Each reply launch is
+    queued right behind its decode launch, before that call's one
+    synchronisation; the send sequencing (self.conns, which an application's
+    encode_messages_multi sends share) and the reply states (self.states) stay
+    on the device."""
+
+    def __init__(self, flow, flags, device="cuda:0"):
+        self.flow, self.flags = flow, flags
+        self.dev = torch.device(device)
+        n = flow.n_conns
+        # a read's replies: its payload bytes and a header per entry and for the open part
+        self.out_slot = (flow.slot + 10 * (flow.msg_cap + 1) + 15) & ~15
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        pin = dict(dtype=torch.uint8, pin_memory=True)
+        self._sizes = dict(out=self.out_slot, res=_lib.TX_RESULT.itemsize, regions=_lib.REPLY_REGION.itemsize)
+        self._d = {k: torch.zeros(n * sz, **u8) for k, sz in self._sizes.items()}
+        self._h = {k: torch.zeros(n * sz, **pin) for k, sz in self._sizes.items()}
+        self.conns = torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
+        self.states = torch.zeros(n * _lib.REPLY_STATE.itemsize, **u8)
+        regions = np.zeros(n, dtype=_lib.REPLY_REGION)   # slot i is read i's, whichever connection that is
+        regions["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(self.out_slot)
+        regions["out_cap"] = self.out_slot
+        self._d["regions"].copy_(torch.from_numpy(regions.view(np.uint8).copy()))
+        self.calls = 0
+        self._replies = None
+
+    def _queued(self, conns, max_len, stream):
+        n, d, f, sz = len(conns), self._d, self.flow._d, self._sizes
+        check("fws_gpu_reply_messages_multi",
+              reply_messages_multi(self.flow.ctx, f["reads"], n, max_len, f["msgs"], f["dst"], f["ctl"], f["mres"],
+                                   d["regions"], d["out"], None, d["res"], self.conns, self.states,
+                                   self.flow.n_conns, self.flags, stream=stream))
+        self.calls += 1
+        for k in ("res", "out"):
+            self._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
+
+    def _synced(self, conns):
+        n = len(conns)
+        res = np.frombuffer(self._h["res"].numpy()[:n * self._sizes["res"]].tobytes(), dtype=_lib.TX_RESULT)
+        for i, c in enumerate(conns):
+            if int(res[i]["status"]):
+                raise FwsError(f"fws_gpu_reply_messages_multi refused the read of connection {c}",
+                               int(res[i]["status"]))
+            o = i * self.out_slot
+            self._replies[c] = self._replies.get(c, b"") + self._h["out"].numpy()[o:o + int(res[i]["out_len"])].tobytes()
+
+    def feed(self, reads):
+        self._replies = {c: b"" for c in reads}
+        self.flow._queued, self.flow._synced = self._queued, self._synced
+        try:
+            units = self.flow.feed(reads)
+        finally:
+            self.flow._queued = self.flow._synced = None
+        return units, self._replies

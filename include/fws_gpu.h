@@ -788,6 +788,115 @@ int fws_gpu_encode_messages_multi(fws_gpu_ctx *ctx, void *dev_out, const void *d
                                   fws_frame_info *dev_frames, fws_tx_result *dev_results,
                                   fws_tx_conn *dev_conns, uint32_t n_conns, void *stream);
 
+/* ---- replies built on the device ----------------------------------------------
+ * The link between the two halves above. OnRecvData answers a completed PING
+ * with a PONG carrying the same payload (w_socket.h:661-666) and a completed
+ * CLOSE with a CLOSE carrying the same payload unless one was sent already
+ * (w_socket.h:667-710); an echo server sends every message back.
+ * fws_gpu_reply_messages_multi reads what fws_gpu_decode_messages_flow or
+ * fws_gpu_decode_messages_multi wrote for dev_reads[0..n) and writes each
+ * read's reply frames into its own region of dev_out, one workgroup per read:
+ * decode -> reply runs on one stream with no host in between. */
+#define FWS_REPLY_CONTROL 1u   /* PING -> PONG, CLOSE -> CLOSE (w_socket.h:661-710) */
+#define FWS_REPLY_ECHO    2u   /* every data part goes back as one frame */
+
+typedef struct fws_reply_state {   /* device memory, one per connection; all zero = new */
+    uint32_t close_sent;   /* 1: this connection's CLOSE has been written (or the host sent one and
+                              set it, the reference's HasSentClose): the call writes nothing more */
+    uint32_t close_code;   /* status code of the CLOSE received: big-endian u16 of its first two
+                              payload bytes, 1005 when it has fewer than two (w_socket.h:668-673); 0 before */
+    uint64_t reserved;     /* 0 */
+} fws_reply_state;         /* 16 bytes */
+
+typedef struct fws_reply_region {  /* device memory, one per read */
+    uint64_t out_off;               /* the read's region of dev_out, 16-B aligned */
+    uint32_t out_cap;
+    uint32_t frame_base, frame_cap; /* its slice of dev_frames (frame_cap 0: no records) */
+    uint32_t reserved0;
+    uint64_t reserved;
+} fws_reply_region;                 /* 32 bytes */
+
+/* dev_reads, n, max_len, dev_msgs, dev_dst, dev_ctl and dev_msg_results are the
+ * decode call's own arguments; the call only reads them. dev_conns is the array
+ * an application hands to fws_gpu_encode_messages_multi for its own sends, so
+ * the two calls sequence one connection's frames through one state. Per read r
+ * (conn = dev_reads[r].conn, offsets relative to the region dev_out + out_off):
+ *   no frames  status 0, n_frames 0, out_len 0, neither state changed, when the
+ *             read's fws_msg_result.status is FWS_ERR_DECLINED or
+ *             FWS_ERR_INVALID; when its decode delivered nothing (n_msgs >
+ *             msg_cap, data_bytes > dst_cap or ctl_bytes > ctl_cap, the
+ *             capacities taken from the read's descriptor); or when
+ *             dev_states[conn].close_sent is set.
+ *   frames    every other status (0, a protocol or sequencing error, a frame-count
+ *             FWS_ERR_CAPACITY) leaves a valid prefix: n_msgs entries, then the
+ *             open part open_off / open_len. In this order:
+ *             1. per entry: opcode 9 with FWS_REPLY_CONTROL one PONG frame, FIN =
+ *                1, payload dev_ctl[ctl_off + off, +len); opcode 10 nothing;
+ *                opcode 8 with FWS_REPLY_CONTROL one CLOSE frame with the same
+ *                payload whatever its length (w_socket.h:693), close_sent = 1
+ *                and close_code set, every later item of the read dropped;
+ *                opcode 1 or 2 with FWS_REPLY_ECHO one data frame, payload
+ *                dev_dst[dst_off + off, +len) (len 0: an empty frame),
+ *                frame_type the entry's opcode, last = 1;
+ *             2. the open part, with FWS_REPLY_ECHO, when open_opcode != 0 and
+ *                open_len > 0: one data frame of [open_off, +open_len), frame_type
+ *                open_opcode, last = 0.
+ *             Opcode and FIN of the data frames are what fws_tx_next(frame_type,
+ *             last, &state, ...) gives, applied in that order from
+ *             dev_conns[conn].last_msg_not_fin: a part whose earlier parts were
+ *             echoed is a continuation by itself; an open part of 0 bytes gives
+ *             no frame, so the frame that completes it carries the opcode.
+ *             Control frames neither use nor change the state.
+ *   bytes     server frames (no MASK bit, no key) back to back from the region's
+ *             start, each what fws_gpu_encode_frames writes for that payload,
+ *             opcode and FIN. No byte outside [out_off, out_off + out_len) is
+ *             written. Sources may have any alignment. Regions must not overlap.
+ *   state     on success dev_conns[conn] gets the new last_msg_not_fin, frames +=
+ *             n_frames, wire_bytes += out_len; dev_states[conn] as above. The
+ *             result echoes the connection's last_msg_not_fin after the call.
+ *   records   dev_frames[frame_base + j], j < min(n_frames, frame_cap), as
+ *             fws_gpu_encode_messages_multi writes them: hdr_off relative to the
+ *             region, key 0. dev_frames may be NULL when every frame_cap is 0.
+ *   refusals  per read; the call still returns 0, nothing is written for that
+ *             read but its result (other fields zero except where stated) and
+ *             both states are untouched. Tested in this order, around the "no
+ *             frames" tests:
+ *               FWS_ERR_INVALID   out_off not 16-B aligned or conn >= n_conns
+ *                                 (before anything else)
+ *               (no frames: the decode's status, an undelivered decode)
+ *               FWS_ERR_INVALID   n_msgs > FWS_MSG_MULTI_MAX_FRAMES + 1 with
+ *                                 n_msgs <= msg_cap: not a decode output
+ *               (no frames: close_sent)
+ *               FWS_ERR_INVALID   an entry no decode writes: a PING or CLOSE over
+ *                                 125 bytes, a data part over
+ *                                 FWS_MSG_MULTI_MAX_READ, an open_opcode not 1 or 2
+ *               FWS_ERR_CAPACITY  the bytes needed exceed out_cap; out_len = the
+ *                                 bytes needed, n_frames is set. The inputs are
+ *                                 intact: the caller may call again with a
+ *                                 larger region.
+ *             Two reads of one call that name the same conn are a contract
+ *             violation: the result is undefined for that connection only.
+ *   max_len   the decode call's value; it selects the workgroup form as there.
+ *   ordering  stream-ordered: no host synchronisation, no copy, no allocation, no
+ *             workspace. Calls queued on one stream chain through dev_conns and
+ *             dev_states; a captured call needs no reset node.
+ * n == 0 returns 0 and looks at nothing. Otherwise ctx and every pointer but
+ * dev_frames must be non-null, dev_out 16-B aligned, max_len between 1 and
+ * FWS_MSG_MULTI_MAX_READ and flags within the two bits defined, or the call
+ * returns FWS_ERR_INVALID before any device call. Out of scope: masked (client)
+ * replies (the decode has no client role yet); cutting a part into several
+ * frames; closing on a protocol error; closing with 1007 for a TEXT entry with
+ * utf8_ok == 0 (it is echoed like any other: that policy stays with the host);
+ * the C++ adapter and the FLoop hook. */
+int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx,
+                                 const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                 const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                 const fws_msg_result *dev_msg_results,
+                                 const fws_reply_region *dev_regions, void *dev_out,
+                                 fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                 fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                 uint32_t flags, void *stream);
+
 /* Host-memory send for one connection: WSocket::SendFrame (w_socket.h:832-944)
  * for its next n frames, in order. Frame i = payloads[i][0..lens[i]) of
  * WSTxFrameType frame_types[i] with last_frame_if_possible = last[i]; a client

@@ -62,11 +62,27 @@ device-to-device copy of the same bytes as a bandwidth reference; the forms
 alternate within each round, and every form's output is compared byte for byte
 first. max_len is the send size, so the small kernel form is the one measured
 up to 16 KiB. One JSON line per grid point.
+--reply measures fws_gpu_reply_messages_multi: n connections
+(64, 512, 4096) x one read each holding one masked single-frame BIN message of
+4 KiB (C1's shape; one send per connection, so the parent can express it), echoed.
+  (i)  the loop, host wall time per step: flow decode -> synchronise -> the host
+       builds fws_tx_send from the copied-back results and entries -> upload ->
+       fws_gpu_encode_messages_multi -> synchronise, all calls from a library
+       built from the parent commit (--parent-lib; two contexts give the A/A
+       spread), against this tree's decode -> reply -> synchronise.
+  (ii) the kernel alone, HIP events around back-to-back launches: the reply
+       launch against the parent's fws_gpu_encode_messages_multi on unmasked
+       one-frame sends of the same payloads (4 KiB and 64 KiB parts); the parent
+       form runs twice per round for its own spread, and the reply launch once
+       more with flags 0 (the entries, the scan and the table, no frame).
+The forms alternate within every round; both paths' output bytes are compared
+first. One JSON line per grid point.
 usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out FILE]
        python tools/msg_bench.py --carry [--parent-lib SO] [--read-mib M] [--target MiB] [--out FILE]
        python tools/msg_bench.py --multi [--grid-n N,N,..] [--grid-kib K,K,..] [--rounds R] [--out FILE]
        python tools/msg_bench.py --flow [--parent-lib SO] [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
-       python tools/msg_bench.py --tx-multi [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]"""
+       python tools/msg_bench.py --tx-multi [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
+       python tools/msg_bench.py --reply --parent-lib SO [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -74,6 +90,7 @@ import os
 import statistics
 import struct
 import sys
+import time
 
 import numpy as np
 import torch
@@ -704,6 +721,159 @@ def tx_multi_bench(n, size, max_frame, rounds, steps):
     return out
 
 
+def walled(fn, steps, warm=10):
+    """Host wall time per step, microseconds; fn ends in its own synchronisation."""
+    for i in range(warm):
+        fn(i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        fn(i)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e6 / steps
+
+
+def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
+    """--reply: see the module docstring. size: the message's payload bytes."""
+    dev = torch.device("cuda:0")
+    P = C.CDLL(parent_lib)
+    for name, res_t, args in _lib.SIGNATURES:
+        if hasattr(P, name):
+            getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
+    assert not hasattr(P, "fws_gpu_reply_messages_multi"), "--parent-lib is this tree's library"
+    rng = np.random.default_rng(31 * n + size)
+    hdr = [header(2, 1, size, int(rng.integers(0, 1 << 32))) for _ in range(min(n, 64))]
+    rlen = len(hdr[0]) + size
+    slot = (rlen + 15) & ~15
+    need = size + (2 if size < 126 else 4 if size <= 65535 else 10)
+    oslot = (need + 15) & ~15
+    host = np.zeros((n, slot), dtype=np.uint8)
+    body = rng.integers(0, 256, (min(n, 64), size), dtype=np.uint8)
+    for r in range(n):
+        host[r, :len(hdr[0])] = np.frombuffer(hdr[r % 64], dtype=np.uint8)
+        host[r, len(hdr[0]):rlen] = body[r % 64]
+    u8 = dict(dtype=torch.uint8, device=dev)
+    pin = dict(dtype=torch.uint8, pin_memory=True)
+    cap, ctl_cap = 2, 16
+    wire = torch.from_numpy(host.reshape(-1)).to(dev)
+    dst, ctl = torch.zeros(n * slot, **u8), torch.zeros(n * ctl_cap, **u8)
+    frames, msgs = torch.zeros(n * cap * 24, **u8), torch.zeros(n * cap * 32, **u8)
+    res, mres = torch.zeros(n * 40, **u8), torch.zeros(n * 64, **u8)
+    flows = torch.zeros(n * _lib.MSG_FLOW.itemsize, **u8)
+    desc = np.zeros(n, dtype=_lib.MSG_READ)
+    regions = np.zeros(n, dtype=_lib.REPLY_REGION)
+    for r in range(n):
+        desc[r] = (r * slot, r * slot, r * ctl_cap, rlen, r, slot, ctl_cap, r * cap, cap, r * cap, cap, 0)
+        regions[r] = (r * oslot, oslot, 0, 0, 0, 0)
+    reads = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    d_regions = torch.from_numpy(regions.view(np.uint8).copy()).to(dev)
+    out_new, out_old = torch.zeros(n * oslot, **u8), torch.zeros(n * oslot, **u8)
+    tres = torch.zeros(n * _lib.TX_RESULT.itemsize, **u8)
+    conns_new, conns_old = torch.zeros(n * _lib.TX_CONN.itemsize, **u8), torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
+    states = torch.zeros(n * _lib.REPLY_STATE.itemsize, **u8)
+    d_sends = torch.zeros(n * _lib.TX_SEND.itemsize, **u8)
+    h_mres, h_msgs, h_sends = torch.zeros(n * 64, **pin), torch.zeros(n * cap * 32, **pin), \
+        torch.zeros(n * _lib.TX_SEND.itemsize, **pin)
+    v_mres = h_mres.numpy().view(_lib.MSG_RESULT)
+    v_msgs = h_msgs.numpy().view(_lib.MSG_INFO).reshape(n, cap)
+    v_sends = h_sends.numpy().view(_lib.TX_SEND)
+    dst_off, out_off = desc["dst_off"].copy(), regions["out_off"].copy()
+    conn_ids = np.arange(n, dtype=np.uint32)
+    ctx = gpu.Ctx(0)
+    s = torch.cuda.current_stream()
+    pctx = []
+    for _ in range(2):
+        h = C.c_void_p()
+        assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0
+        pctx.append(h)
+    max_len = rlen
+
+    def p_decode(h):
+        assert P.fws_gpu_decode_messages_flow(h, wire.data_ptr(), reads.data_ptr(), n, max_len, frames.data_ptr(),
+                                              msgs.data_ptr(), dst.data_ptr(), ctl.data_ptr(), res.data_ptr(),
+                                              mres.data_ptr(), flows.data_ptr(), n, s.cuda_stream) == 0
+
+    def p_encode(h):
+        assert P.fws_gpu_encode_messages_multi(h, out_old.data_ptr(), dst.data_ptr(), d_sends.data_ptr(), n, size,
+                                               None, tres.data_ptr(), conns_old.data_ptr(), n, s.cuda_stream) == 0
+
+    def build_sends():
+        """The host walk: one completed message per read, echoed as one send (vectorised over the reads)."""
+        assert (v_mres["status"] == 0).all() and (v_mres["n_msgs"] == 1).all()
+        e = v_msgs[:, 0]
+        v_sends["src_off"], v_sends["out_off"], v_sends["len"] = dst_off + e["off"], out_off, e["len"]
+        v_sends["out_cap"], v_sends["conn"], v_sends["max_frame"], v_sends["key"] = oslot, conn_ids, 0, 0
+        v_sends["frame_type"], v_sends["last"], v_sends["masked"] = e["opcode"], 1, 0
+
+    def old_loop(h):
+        def f(i):
+            p_decode(h)
+            h_mres.copy_(mres, non_blocking=True)
+            h_msgs.copy_(msgs, non_blocking=True)
+            s.synchronize()
+            build_sends()
+            d_sends.copy_(h_sends, non_blocking=True)
+            p_encode(h)
+            s.synchronize()
+        return f
+
+    # (raw pointers, as the parent's calls above: the Python wrapper's argument conversion costs more host time
+    # than a small launch takes on the device, and the events would time the host)
+    reply_fn = _lib.lib().fws_gpu_reply_messages_multi
+    rp = [t.data_ptr() for t in (reads, msgs, dst, ctl, mres, d_regions, out_new, tres, conns_new, states)]
+
+    def f_reply(i, flags=_lib.FWS_REPLY_CONTROL | _lib.FWS_REPLY_ECHO):
+        assert reply_fn(ctx.h, rp[0], n, max_len, rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], None, rp[7], rp[8],
+                        rp[9], n, flags, s.cuda_stream) == 0
+
+    decode_fn = _lib.lib().fws_gpu_decode_messages_flow
+    dp = [t.data_ptr() for t in (wire, reads, frames, msgs, dst, ctl, res, mres, flows)]
+
+    def new_loop(i):
+        assert decode_fn(ctx.h, dp[0], dp[1], n, max_len, dp[2], dp[3], dp[4], dp[5], dp[6], dp[7], dp[8], n,
+                         s.cuda_stream) == 0
+        f_reply(i)
+        s.synchronize()
+
+    # checked first: both paths write the same frames
+    old_loop(pctx[0])(0)
+    new_loop(0)
+    t = np.frombuffer(tres.cpu().numpy().tobytes(), dtype=_lib.TX_RESULT)
+    assert (t["status"] == 0).all() and (t["out_len"] == need).all() and (t["n_frames"] == 1).all()
+    assert torch.equal(out_new, out_old) and int(out_new.view(n, oslot)[:, 0].min()) == 0x82
+    assert torch.equal(conns_new, conns_old)
+    out = {"measure": "reply", "n": n, "part_bytes": size, "form": "small" if rlen <= (16 << 10) else "full",
+           "reply_bytes": n * need, "rounds": rounds, "steps": steps, "device": torch.cuda.get_device_name(0),
+           "parent_lib": os.path.basename(parent_lib)}
+    forms = {}
+    if loop:
+        forms.update({"loop_parent_a": (walled, old_loop(pctx[0])), "loop_parent_b": (walled, old_loop(pctx[1])),
+                      "loop_reply": (walled, new_loop)})
+    forms.update({"k_tx_multi_a": (timed, lambda i: p_encode(pctx[0])), "k_tx_multi_b": (timed, lambda i: p_encode(pctx[1])),
+                  "k_reply": (timed, f_reply),
+                  # flags 0: the entries read, the scan and the table, no frame (where the time of a small call goes)
+                  "k_reply_no_frames": (timed, lambda i: f_reply(i, 0))})
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(forms[k][0](forms[k][1], steps))
+    for k in forms:
+        out[k + "_us"] = round(statistics.median(times[k]), 2)
+        out[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    if loop:
+        base = min(out["loop_parent_a_us"], out["loop_parent_b_us"])
+        out["loop_aa_spread_us"] = round(abs(out["loop_parent_a_us"] - out["loop_parent_b_us"]), 2)
+        out["loop_parent_over_reply"] = round(base / out["loop_reply_us"], 2)
+    kb = min(out["k_tx_multi_a_us"], out["k_tx_multi_b_us"])
+    out["k_aa_spread_us"] = round(abs(out["k_tx_multi_a_us"] - out["k_tx_multi_b_us"]), 2)
+    out["k_reply_over_tx_multi"] = round(out["k_reply_us"] / kb, 3)
+    out["k_reply_gb_s"] = round(n * need / out["k_reply_us"] / 1e3, 2)
+    for h in pctx:
+        P.fws_gpu_ctx_destroy(h)
+    ctx.close()
+    return out
+
+
 def c3_stream(target):
     wire, descs, _ = gpu.config_c3(target=target)
     regions = np.zeros(len(descs), dtype=_lib.FRAME_DESC)
@@ -810,9 +980,25 @@ def main():
     ap.add_argument("--flow-frame-kib", type=int, default=1024, help="--flow (ii): a frame on the wire, KiB")
     ap.add_argument("--flow-read-kib", type=int, default=16, help="--flow (ii): a read, KiB")
     ap.add_argument("--tx-multi", action="store_true", help="measure fws_gpu_encode_messages_multi (see above)")
+    ap.add_argument("--reply", action="store_true", help="measure fws_gpu_reply_messages_multi (see above)")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.reply:
+        assert a.parent_lib, "--reply needs --parent-lib"
+        grid_n = "64,512,4096" if a.grid_n == ap.get_default("grid_n") else a.grid_n
+        grid_kib = "4,64" if a.grid_kib == ap.get_default("grid_kib") else a.grid_kib
+        for kib in map(int, grid_kib.split(",")):
+            for n in map(int, grid_n.split(",")):
+                if n * (kib << 10) > (64 << 20):          # (the kernel comparison at 64 KiB: up to 1024 connections)
+                    continue
+                lines.append(json.dumps(reply_bench(n, kib << 10, os.path.abspath(a.parent_lib), a.rounds, a.steps,
+                                                    loop=kib == 4)))
+                print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.tx_multi:
         grid_n = "1,64,512" if a.grid_n == ap.get_default("grid_n") else a.grid_n
         points = [(n, kib << 10, 0) for kib in map(int, a.grid_kib.split(",")) for n in map(int, grid_n.split(","))]
