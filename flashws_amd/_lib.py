@@ -96,10 +96,24 @@ assert TX_CONN.itemsize == 32 and TX_SEND.itemsize == 64 and TX_RESULT.itemsize 
 # fws_gpu_reply_messages_multi: what is answered, the connection's reply state and a read's output region
 FWS_REPLY_CONTROL = 1   # PING -> PONG, CLOSE -> CLOSE
 FWS_REPLY_ECHO = 2      # every data part goes back as one frame
-REPLY_STATE = np.dtype([("close_sent", "<u4"), ("close_code", "<u4"), ("reserved", "<u8")])
+REPLY_STATE = np.dtype([("close_sent", "<u4"), ("close_code", "<u4"), ("fail_code", "<u4"), ("reserved", "<u4")])
 REPLY_REGION = np.dtype([("out_off", "<u8"), ("out_cap", "<u4"), ("frame_base", "<u4"), ("frame_cap", "<u4"),
                          ("reserved0", "<u4"), ("reserved", "<u8")])
 assert REPLY_STATE.itemsize == 16 and REPLY_REGION.itemsize == 32
+# fws_gpu_reply_messages_strict: the status codes of the CLOSE that fails a connection (RFC 6455 §7.4.1)
+FWS_CLOSE_PROTOCOL_ERROR = 1002   # a malformed CLOSE, a bad status code, a decode that ended in a protocol error
+FWS_CLOSE_INVALID_DATA = 1007     # a TEXT message or a CLOSE reason that is not UTF-8
+FWS_CLOSE_TOO_BIG = 1009          # a message over max_message_bytes, a frame over 2^32 bytes
+# the decode statuses answered with 1002; FWS_ERR_TOO_LARGE is answered with 1009
+FWS_PROTOCOL_ERRORS = (FWS_ERR_RSV, FWS_ERR_NOT_MASKED, FWS_ERR_MASKED, FWS_ERR_OPCODE, FWS_ERR_CONTROL_FRAME,
+                       FWS_ERR_SEQUENCE)
+
+
+def close_code_valid(code):
+    """Whether a status code may appear in a CLOSE frame: the registry as of RFC 6455 plus 1012-1014."""
+    return 1000 <= code <= 1003 or 1007 <= code <= 1014 or 3000 <= code <= 4999
+
+
 assert DECODE_RESULT.itemsize == 40 and RX_EVENT.itemsize == 48
 RX_READ = np.dtype([("conn", "<u4"), ("flags", "<u4"), ("buf", "<u8"), ("size", "<u8"), ("capacity", "<u8")])
 RX_READ_RESULT = np.dtype([("ret", "<i4"), ("pad", "<u4"), ("events", "<u8"), ("n_events", "<u8"),
@@ -171,6 +185,8 @@ SIGNATURES = [
     ("fws_gpu_encode_messages_multi", _I, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _U32, _P]),
     ("fws_gpu_reply_messages_multi", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _U32,
                                           _P]),
+    ("fws_gpu_reply_messages_strict", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P, _P, _P,
+                                           _U32, _U32, _P]),
     ("fws_tx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_tx_session_destroy", None, [_P]),
     ("fws_tx_session_send", _I, [_P, _P, _P, _P, _P, _P, _U32, _P, _U64, _PU64]),

@@ -533,6 +533,29 @@ int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads
                             dev_states, n_conns, flags, (hipStream_t)stream);
 }
 
+int fws_gpu_reply_messages_strict(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                  const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                  const fws_msg_result *dev_msg_results, const void *dev_conn_states,
+                                  uint32_t conn_state_stride, uint64_t max_message_bytes,
+                                  const fws_reply_region *dev_regions, void *dev_out, fws_frame_info *dev_frames,
+                                  fws_tx_result *dev_results, fws_tx_conn *dev_conns, fws_reply_state *dev_states,
+                                  uint32_t n_conns, uint32_t flags, void *stream) {
+    if (n == 0) return 0;
+    // (dev_frames may be null: a read with frame_cap 0 writes no record)
+    if (!ctx || !dev_reads || !dev_msgs || !dev_dst || !dev_ctl || !dev_msg_results || !dev_conn_states ||
+        !dev_regions || !dev_out || !dev_results || !dev_conns || !dev_states)
+        return FWS_ERR_INVALID;
+    if (conn_state_stride != sizeof(fws_msg_carry) && conn_state_stride != sizeof(fws_msg_flow)) return FWS_ERR_INVALID;
+    if (((uintptr_t)dev_out & 15u) != 0) return FWS_ERR_INVALID;
+    if (max_len < 1u || max_len > FWS_MSG_MULTI_MAX_READ) return FWS_ERR_INVALID;
+    if (flags & ~(FWS_REPLY_CONTROL | FWS_REPLY_ECHO)) return FWS_ERR_INVALID;
+    if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
+    return fws_launch_reply_strict(dev_reads, n, max_len, dev_msgs, (const uint8_t *)dev_dst, (const uint8_t *)dev_ctl,
+                                   dev_msg_results, (const uint8_t *)dev_conn_states, conn_state_stride,
+                                   max_message_bytes, dev_regions, (uint8_t *)dev_out, dev_frames, dev_results,
+                                   dev_conns, dev_states, n_conns, flags, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 int fws_decode_prepare(fws_gpu_ctx *ctx, uint64_t len, uint32_t cap, bool utf8) {

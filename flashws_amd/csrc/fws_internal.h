@@ -354,6 +354,15 @@ int fws_launch_reply(const fws_msg_read *reads, uint32_t n, uint32_t max_len, co
                      const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
                      const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames, fws_tx_result *res,
                      fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns, uint32_t flags, hipStream_t s);
+
+// fws_gpu_reply_messages_strict (reply_strict_kernels.hip): the same with the first failing item of a read answered
+// by a CLOSE that carries the status code; conn_states is the decode call's state array (stride 64 or 96), read only.
+int fws_launch_reply_strict(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
+                            const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
+                            const uint8_t *conn_states, uint32_t conn_state_stride, uint64_t max_message_bytes,
+                            const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames, fws_tx_result *res,
+                            fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns, uint32_t flags,
+                            hipStream_t s);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
                        hipStream_t s, const uint32_t *deny = nullptr);

@@ -1098,6 +1098,25 @@ def reply_messages_multi(ctx, reads, n, max_len, msgs, dst, ctl, msg_results, re
                                               _ptr(conns), _ptr(states), n_conns, flags, _stream_handle(stream))
 
 
+def reply_messages_strict(ctx, reads, n, max_len, msgs, dst, ctl, msg_results, conn_states, conn_state_stride,
+                          max_message_bytes, regions, out, frames, results, conns, states, n_conns, flags, stream=None):
+    """fws_gpu_reply_messages_strict: reply_messages_multi for a server that
+    fails connections on the device. conn_states is the decode call's own state
+    tensor (fws_msg_carry records, conn_state_stride 64, after
+    decode_messages_multi; fws_msg_flow records, 96, after decode_messages_flow),
+    read only; max_message_bytes bounds a message (0: no limit). A read's first
+    failing item -- a message over the limit, a TEXT message or CLOSE reason that
+    is not UTF-8, a malformed CLOSE, a decode that ended in a protocol error --
+    is answered with a CLOSE carrying 1009, 1007 or 1002, nothing follows it and
+    fws_reply_state.fail_code keeps the code. Returns the call's status; nothing
+    is synchronised."""
+    return lib().fws_gpu_reply_messages_strict(ctx.h, _ptr(reads), n, max_len, _ptr(msgs), _ptr(dst), _ptr(ctl),
+                                               _ptr(msg_results), _ptr(conn_states), conn_state_stride,
+                                               max_message_bytes, _ptr(regions), _ptr(out),
+                                               _ptr(frames) if frames is not None else None, _ptr(results),
+                                               _ptr(conns), _ptr(states), n_conns, flags, _stream_handle(stream))
+
+
 def read_reply_state(states, conn=0):
     sz = _lib.REPLY_STATE.itemsize
     return np.frombuffer(states[conn * sz:(conn + 1) * sz].cpu().numpy().tobytes(), dtype=_lib.REPLY_STATE)[0]
@@ -1112,14 +1131,22 @@ class MessageResponder:
     queued right behind its decode launch, before that call's one
     synchronisation; the send sequencing (self.conns, which an application's
     encode_messages_multi sends share) and the reply states (self.states) stay
-    on the device."""
+    on the device. With strict=True the launches are
+    fws_gpu_reply_messages_strict over flow's state tensor: a connection that
+    breaks the protocol, sends a TEXT message or CLOSE reason that is not UTF-8
+    or a message over max_message bytes (0: no limit) gets its valid prefix
+    answered and then a CLOSE with the status code; failed = {conn: code} lists
+    these connections (flow.status[conn] keeps a decode error as before, and
+    the host drops the connection)."""
 
-    def __init__(self, flow, flags, device="cuda:0"):
-        self.flow, self.flags = flow, flags
+    def __init__(self, flow, flags, device="cuda:0", strict=False, max_message=0):
+        self.flow, self.flags, self.strict, self.max_message = flow, flags, bool(strict), int(max_message)
+        self.failed = {}
         self.dev = torch.device(device)
         n = flow.n_conns
         # a read's replies: its payload bytes and a header per entry and for the open part
-        self.out_slot = (flow.slot + 10 * (flow.msg_cap + 1) + 15) & ~15
+        # (strict: and the 4 bytes of the failing CLOSE)
+        self.out_slot = (flow.slot + 10 * (flow.msg_cap + 1) + (4 if self.strict else 0) + 15) & ~15
         u8 = dict(dtype=torch.uint8, device=self.dev)
         pin = dict(dtype=torch.uint8, pin_memory=True)
         self._sizes = dict(out=self.out_slot, res=_lib.TX_RESULT.itemsize, regions=_lib.REPLY_REGION.itemsize)
@@ -1127,6 +1154,7 @@ class MessageResponder:
         self._h = {k: torch.zeros(n * sz, **pin) for k, sz in self._sizes.items()}
         self.conns = torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
         self.states = torch.zeros(n * _lib.REPLY_STATE.itemsize, **u8)
+        self._h_states = torch.zeros(n * _lib.REPLY_STATE.itemsize, **pin)
         regions = np.zeros(n, dtype=_lib.REPLY_REGION)   # slot i is read i's, whichever connection that is
         regions["out_off"] = np.arange(n, dtype=np.uint64) * np.uint64(self.out_slot)
         regions["out_cap"] = self.out_slot
@@ -1136,13 +1164,22 @@ class MessageResponder:
 
     def _queued(self, conns, max_len, stream):
         n, d, f, sz = len(conns), self._d, self.flow._d, self._sizes
-        check("fws_gpu_reply_messages_multi",
-              reply_messages_multi(self.flow.ctx, f["reads"], n, max_len, f["msgs"], f["dst"], f["ctl"], f["mres"],
-                                   d["regions"], d["out"], None, d["res"], self.conns, self.states,
-                                   self.flow.n_conns, self.flags, stream=stream))
+        if self.strict:
+            check("fws_gpu_reply_messages_strict",
+                  reply_messages_strict(self.flow.ctx, f["reads"], n, max_len, f["msgs"], f["dst"], f["ctl"], f["mres"],
+                                        self.flow.flows, _lib.MSG_FLOW.itemsize, self.max_message, d["regions"],
+                                        d["out"], None, d["res"], self.conns, self.states, self.flow.n_conns,
+                                        self.flags, stream=stream))
+        else:
+            check("fws_gpu_reply_messages_multi",
+                  reply_messages_multi(self.flow.ctx, f["reads"], n, max_len, f["msgs"], f["dst"], f["ctl"], f["mres"],
+                                       d["regions"], d["out"], None, d["res"], self.conns, self.states,
+                                       self.flow.n_conns, self.flags, stream=stream))
         self.calls += 1
         for k in ("res", "out"):
             self._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
+        if self.strict:
+            self._h_states.copy_(self.states, non_blocking=True)
 
     def _synced(self, conns):
         n = len(conns)
@@ -1153,6 +1190,11 @@ class MessageResponder:
                                int(res[i]["status"]))
             o = i * self.out_slot
             self._replies[c] = self._replies.get(c, b"") + self._h["out"].numpy()[o:o + int(res[i]["out_len"])].tobytes()
+        if self.strict:
+            states = np.frombuffer(self._h_states.numpy().tobytes(), dtype=_lib.REPLY_STATE)
+            for c in conns:
+                if int(states[c]["fail_code"]):
+                    self.failed[c] = int(states[c]["fail_code"])
 
     def feed(self, reads):
         self._replies = {c: b"" for c in reads}

@@ -270,7 +270,8 @@ typedef struct fws_msg_result {
  * Every call starts from "no message open"; a connection whose bytes arrive in
  * reads uses fws_gpu_decode_messages_carry below, which carries the open
  * message and its UTF-8 state from call to call.
- * Out of scope: UTF-8 validation of CLOSE reasons, client-side streams, the C++
+ * A CLOSE reason is validated where the CLOSE is answered
+ * (fws_gpu_reply_messages_strict). Out of scope: client-side streams, the C++
  * adapter and the FLoop hook. */
 int fws_gpu_decode_messages(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len,
                             fws_frame_info *dev_frames, uint32_t cap,
@@ -349,8 +350,8 @@ typedef struct fws_msg_carry {   /* device memory; all zero = a new connection *
  *             dev_ctl, *dev_carry is left exactly as found and resume_off = 0
  *             (the counts are still reported): the caller retries the same
  *             bytes with larger buffers.
- * Out of scope: resuming inside a frame's payload, UTF-8 validation of CLOSE
- * reasons, client-side streams, the C++ adapter and the FLoop hook. */
+ * Out of scope: resuming inside a frame's payload, client-side streams, the C++
+ * adapter and the FLoop hook. */
 int fws_gpu_decode_messages_carry(fws_gpu_ctx *ctx, const void *dev_wire, uint64_t len,
                                   fws_frame_info *dev_frames, uint32_t cap,
                                   fws_msg_info *dev_msgs, uint32_t msg_cap,
@@ -500,9 +501,8 @@ typedef struct fws_msg_flow {      /* device memory; all zero = a new connection
  *             always enough.
  * A read longer than FWS_MSG_MULTI_MAX_READ is cut anywhere into pieces whose
  * calls are queued on one stream; they chain through dev_flows without the
- * host. Out of scope: the same for fws_gpu_decode_messages(_carry), UTF-8
- * validation of CLOSE reasons, client-side streams, the C++ adapter and the
- * FLoop hook. */
+ * host. Out of scope: the same for fws_gpu_decode_messages(_carry), client-side
+ * streams, the C++ adapter and the FLoop hook. */
 int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire,
                                  const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
                                  fws_frame_info *dev_frames, fws_msg_info *dev_msgs,
@@ -805,7 +805,10 @@ typedef struct fws_reply_state {   /* device memory, one per connection; all zer
                               set it, the reference's HasSentClose): the call writes nothing more */
     uint32_t close_code;   /* status code of the CLOSE received: big-endian u16 of its first two
                               payload bytes, 1005 when it has fewer than two (w_socket.h:668-673); 0 before */
-    uint64_t reserved;     /* 0 */
+    uint32_t fail_code;    /* fws_gpu_reply_messages_strict: the status code this side sent when it failed
+                              the connection (1002, 1007 or 1009); 0 otherwise, and always 0 from
+                              fws_gpu_reply_messages_multi */
+    uint32_t reserved;     /* 0 */
 } fws_reply_state;         /* 16 bytes */
 
 typedef struct fws_reply_region {  /* device memory, one per read */
@@ -885,9 +888,10 @@ typedef struct fws_reply_region {  /* device memory, one per read */
  * FWS_MSG_MULTI_MAX_READ and flags within the two bits defined, or the call
  * returns FWS_ERR_INVALID before any device call. Out of scope: masked (client)
  * replies (the decode has no client role yet); cutting a part into several
- * frames; closing on a protocol error; closing with 1007 for a TEXT entry with
- * utf8_ok == 0 (it is echoed like any other: that policy stays with the host);
- * the C++ adapter and the FLoop hook. */
+ * frames; the C++ adapter and the FLoop hook. This call answers whatever the
+ * decode delivered -- a TEXT entry with utf8_ok == 0 is echoed like any other, a
+ * decode that ended in a protocol error gets the replies to its valid prefix;
+ * fws_gpu_reply_messages_strict below fails such a connection instead. */
 int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx,
                                  const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
                                  const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
@@ -896,6 +900,90 @@ int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx,
                                  fws_frame_info *dev_frames, fws_tx_result *dev_results,
                                  fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
                                  uint32_t flags, void *stream);
+
+/* ---- the same for a server that fails connections on the device ---------------
+ * RFC 6455 §7.1.7 ("Fail the WebSocket Connection"), §5.5.1, §7.4 and §8.1: a
+ * peer that breaks the protocol, sends a TEXT message or a CLOSE reason that is
+ * not UTF-8, or a message larger than the server accepts is answered with a
+ * CLOSE frame carrying a status code, and nothing more is sent.
+ * fws_gpu_reply_messages_strict is fws_gpu_reply_messages_multi with that rule
+ * applied on the device, from the verdicts the decode already left there; no
+ * host walk of results and entries between decode and reply.
+ *   dev_conn_states / conn_state_stride  the decode call's own state array, which
+ *             the call only reads: fws_msg_carry records (stride 64) after
+ *             fws_gpu_decode_messages_multi, fws_msg_flow records (stride 96,
+ *             the carry first) after fws_gpu_decode_messages_flow; record
+ *             dev_reads[r].conn is read r's.
+ *   max_message_bytes  the largest message accepted, all its parts counted;
+ *             0: no limit.
+ * Every other argument, flags included, is fws_gpu_reply_messages_multi's, and
+ * everything that call's contract says holds unchanged: the "no frames" cases,
+ * the refusals and their order, bytes, records, states, max_len, ordering, no
+ * workspace. A read with no failing item gets, byte for byte, what
+ * fws_gpu_reply_messages_multi writes. What is added: each item of a read --
+ * its n_msgs entries in order, then the open part, then, last, the decode's
+ * error -- has a failure code or none, the first row that applies:
+ *   TEXT / BIN entry  max_message_bytes > 0 and (prev_open_bytes of the state if
+ *                     the entry is FWS_MSG_CONTINUED, else 0) + len exceeds it   1009
+ *   TEXT entry        utf8_ok == 0                                                1007
+ *   the open part     (judged whether or not open_len is 0) max_message_bytes > 0
+ *                     and the state's open_bytes (stride 96: open_bytes +
+ *                     frame_unread) exceeds it: a frame that announces too much
+ *                     fails in the read that holds its header                    1009
+ *   the open part     open_opcode == 1 and the state's utf8_bad is set: the early
+ *                     failure §8.1 allows                                         1007
+ *   CLOSE entry       len == 1                                                    1002
+ *   CLOSE entry       len >= 2 and a status code outside 1000-1003, 1007-1014,
+ *                     3000-4999 (the IANA registry as of RFC 6455 and 1012-1014;
+ *                     1004-1006, 1015, anything below 1000, 1016-2999 and
+ *                     anything from 5000 on may not appear in a frame)            1002
+ *   CLOSE entry       len > 2 and bytes [2, len) are not well-formed UTF-8 as a
+ *                     whole string (Unicode Table 3-7; a sequence cut by the end
+ *                     is malformed)                                               1007
+ *   the decode's error  status == FWS_ERR_TOO_LARGE                               1009
+ *   the decode's error  status FWS_ERR_RSV, FWS_ERR_NOT_MASKED, FWS_ERR_MASKED,
+ *                     FWS_ERR_OPCODE, FWS_ERR_CONTROL_FRAME or FWS_ERR_SEQUENCE   1002
+ * Only the read's first CLOSE entry is judged, whatever flags is: with
+ * FWS_REPLY_CONTROL nothing follows it, without it the CLOSE and what follows are
+ * the host's. A CLOSE of length 0 or with a valid code and reason, a PING and a
+ * PONG never fail. FWS_ERR_CAPACITY statuses, undelivered decodes and
+ * FWS_ERR_DECLINED / FWS_ERR_INVALID reads are not failures and are treated as
+ * by fws_gpu_reply_messages_multi.
+ * Let f be the first failing item and c the first CLOSE entry answered (with
+ * FWS_REPLY_CONTROL). With no f, or c < f, the read is answered as by
+ * fws_gpu_reply_messages_multi. Otherwise the items before f are answered as
+ * there; in f's place goes one CLOSE frame, FIN = 1, whose payload is the code's
+ * two big-endian bytes (no reason), whatever flags is, 0 included; every later
+ * item is dropped; dev_states[conn] gets close_sent = 1 and fail_code = the
+ * code, and close_code as above if f was a CLOSE entry, else it is left as it
+ * was. The open part is sent before the failing frame only when f is the
+ * decode's error. A close_sent found set still means "no frames".
+ *   capacity  the bytes and the frame count include the failing frame (4 bytes);
+ *             on FWS_ERR_CAPACITY nothing is written and both states are intact.
+ *   refusals  one more, tested just before FWS_ERR_CAPACITY: FWS_ERR_INVALID for
+ *             more than FWS_MSG_MULTI_MAX_FRAMES + 2 frames (257 entries, an open
+ *             part and an error: not a decode output).
+ * The reference's server closes with 1006 and an error text on such errors
+ * (ws_server_socket.h:176-181). RFC 6455 §7.4.1 reserves 1006 and forbids it in
+ * a frame; this call follows the RFC. The FLoop hook, which reproduces the
+ * reference's text, is untouched.
+ * n == 0 returns 0 and looks at nothing. Otherwise the checks of
+ * fws_gpu_reply_messages_multi apply, dev_conn_states must be non-null and
+ * conn_state_stride 64 or 96, or the call returns FWS_ERR_INVALID before any
+ * device call. Out of scope: a reason in the failing CLOSE; masked (client)
+ * replies; cutting a part into several frames; a limit per connection; stopping
+ * the decode of a failed connection (the host drops it when it sees fail_code);
+ * the C++ adapter and the FLoop hook. */
+int fws_gpu_reply_messages_strict(fws_gpu_ctx *ctx,
+                                  const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                  const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                  const fws_msg_result *dev_msg_results,
+                                  const void *dev_conn_states, uint32_t conn_state_stride,
+                                  uint64_t max_message_bytes,
+                                  const fws_reply_region *dev_regions, void *dev_out,
+                                  fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                  fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                  uint32_t flags, void *stream);
 
 /* Host-memory send for one connection: WSocket::SendFrame (w_socket.h:832-944)
  * for its next n frames, in order. Frame i = payloads[i][0..lens[i]) of

@@ -82,7 +82,17 @@ usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out 
        python tools/msg_bench.py --multi [--grid-n N,N,..] [--grid-kib K,K,..] [--rounds R] [--out FILE]
        python tools/msg_bench.py --flow [--parent-lib SO] [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
        python tools/msg_bench.py --tx-multi [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
-       python tools/msg_bench.py --reply --parent-lib SO [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]"""
+       python tools/msg_bench.py --reply --parent-lib SO [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
+
+--reply-strict measures fws_gpu_reply_messages_strict: the
+echo of --reply (ii) with no failing item, n in {64, 512, 4096} x 4 KiB and 512
+x 64 KiB, and one row where every read is a CLOSE of one byte and fails. HIP
+events around back-to-back launches through raw pointers; within each round,
+alternating: this tree's fws_gpu_reply_messages_multi, the same call of a
+library built from the parent commit in two contexts (the A/A spread), and the
+strict call. Every form's output is compared byte for byte first. SO is the
+parent commit's library (it has the plain call and lacks the strict one).
+       python tools/msg_bench.py --reply-strict --parent-lib SO [--rounds R] [--steps S] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -874,6 +884,127 @@ def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
     return out
 
 
+def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
+    """--reply-strict: see the module docstring. size: the message's payload
+    bytes; fail: every read is a CLOSE frame of one byte instead, which the
+    strict call answers with 1002 from its constant source."""
+    dev = torch.device("cuda:0")
+    P = C.CDLL(parent_lib)
+    for name, res_t, args in _lib.SIGNATURES:
+        if hasattr(P, name):
+            getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
+    assert hasattr(P, "fws_gpu_reply_messages_multi") and not hasattr(P, "fws_gpu_reply_messages_strict"), \
+        "--parent-lib is not the parent commit's library"
+    if fail:
+        size = 1
+    rng = np.random.default_rng(37 * n + size)
+    hdr = [header(8 if fail else 2, 1, size, int(rng.integers(0, 1 << 32))) for _ in range(min(n, 64))]
+    rlen = len(hdr[0]) + size
+    slot = (rlen + 15) & ~15
+    need = 4 if fail else size + (2 if size < 126 else 4 if size <= 65535 else 10)
+    oslot = (max(need, size + 2) + 15) & ~15
+    host = np.zeros((n, slot), dtype=np.uint8)
+    body = rng.integers(0, 256, (min(n, 64), size), dtype=np.uint8)
+    for r in range(n):
+        host[r, :len(hdr[0])] = np.frombuffer(hdr[r % 64], dtype=np.uint8)
+        host[r, len(hdr[0]):rlen] = body[r % 64]
+    u8 = dict(dtype=torch.uint8, device=dev)
+    cap, ctl_cap = 2, 16
+    wire = torch.from_numpy(host.reshape(-1)).to(dev)
+    dst, ctl = torch.zeros(n * slot, **u8), torch.zeros(n * ctl_cap, **u8)
+    frames, msgs = torch.zeros(n * cap * 24, **u8), torch.zeros(n * cap * 32, **u8)
+    res, mres = torch.zeros(n * 40, **u8), torch.zeros(n * 64, **u8)
+    flows = torch.zeros(n * _lib.MSG_FLOW.itemsize, **u8)
+    desc = np.zeros(n, dtype=_lib.MSG_READ)
+    regions = np.zeros(n, dtype=_lib.REPLY_REGION)
+    for r in range(n):
+        desc[r] = (r * slot, r * slot, r * ctl_cap, rlen, r, slot, ctl_cap, r * cap, cap, r * cap, cap, 0)
+        regions[r] = (r * oslot, oslot, 0, 0, 0, 0)
+    reads = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    d_regions = torch.from_numpy(regions.view(np.uint8).copy()).to(dev)
+    ctx = gpu.Ctx(0)
+    s = torch.cuda.current_stream()
+    pctx = []
+    for _ in range(2):
+        h = C.c_void_p()
+        assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0
+        pctx.append(h)
+    max_len = rlen
+    assert gpu.decode_messages_flow(ctx, wire, reads, n, max_len, frames, msgs, dst, ctl, res, mres, flows, n) == 0
+    torch.cuda.synchronize()
+    # A CLOSE answered sets close_sent and the next call on that state is silent, so every launch of a measurement
+    # gets a fresh state array out of a pool (all forms alike; zeroed outside the timed launches).
+    ssz, pool = n * _lib.REPLY_STATE.itemsize, steps + 10
+    states = torch.zeros(pool * ssz, **u8)
+    both = _lib.FWS_REPLY_CONTROL | _lib.FWS_REPLY_ECHO
+    ptr = [t.data_ptr() for t in (reads, msgs, dst, ctl, mres, d_regions, flows)]
+
+    # the timed launches of every form write into one set of buffers, so that where a buffer lies is no difference
+    # between the forms; the check before them gives each form its own
+    shared = [torch.zeros(n * oslot, **u8), torch.zeros(n * _lib.TX_RESULT.itemsize, **u8),
+              torch.zeros(n * _lib.TX_CONN.itemsize, **u8)]
+
+    def form(fn, h, strict, flags=both):
+        own = [torch.zeros_like(x) for x in shared]
+        k = [0]
+        extra = (ptr[6], _lib.MSG_FLOW.itemsize, 0) if strict else ()
+
+        def launch(bufs):
+            o, t, c = (x.data_ptr() for x in bufs)
+            st = states.data_ptr() + (k[0] % pool) * ssz
+            k[0] += 1
+            assert fn(h, ptr[0], n, max_len, ptr[1], ptr[2], ptr[3], ptr[4], *extra, ptr[5], o, None, t, c, st, n, flags,
+                      s.cuda_stream) == 0
+
+        def measure(steps):
+            states.zero_()
+            k[0] = 0
+            return timed(lambda i: launch(shared), steps)
+        return dict(f=lambda i: launch(own), measure=measure, out=own[0], res=own[1], conns=own[2])
+
+    L = _lib.lib()
+    forms = {"k_reply": form(L.fws_gpu_reply_messages_multi, ctx.h, False),
+             "k_reply_parent_a": form(P.fws_gpu_reply_messages_multi, pctx[0], False),
+             "k_reply_parent_b": form(P.fws_gpu_reply_messages_multi, pctx[1], False),
+             "k_reply_strict": form(L.fws_gpu_reply_messages_strict, ctx.h, True)}
+    # flags 0: the entries read, the minima, the scan and the table, no frame unless a read fails
+    front = {"k_reply_no_frames": form(L.fws_gpu_reply_messages_multi, ctx.h, False, 0),
+             "k_reply_strict_no_frames": form(L.fws_gpu_reply_messages_strict, ctx.h, True, 0)}
+    # checked first: every form's output, byte for byte
+    for v in forms.values():
+        states.zero_()
+        v["f"](0)
+    torch.cuda.synchronize()
+    a, st = forms["k_reply"], np.frombuffer(states[:ssz].cpu().numpy().tobytes(), dtype=_lib.REPLY_STATE)
+    for k in ("k_reply_parent_a", "k_reply_parent_b") + (() if fail else ("k_reply_strict",)):
+        assert all(torch.equal(a[x], forms[k][x]) for x in ("out", "res", "conns")), k
+    t = np.frombuffer(forms["k_reply_strict"]["res"].cpu().numpy().tobytes(), dtype=_lib.TX_RESULT)
+    assert (t["status"] == 0).all() and (t["out_len"] == need).all() and (t["n_frames"] == 1).all()
+    assert (st["fail_code"] == (1002 if fail else 0)).all() and (st["close_sent"] == int(fail)).all()
+    if fail:
+        got = forms["k_reply_strict"]["out"].view(n, oslot)[:, :4].cpu().numpy()
+        assert (got == np.frombuffer(bytes.fromhex("880203EA"), dtype=np.uint8)).all()
+    out = {"measure": "reply_strict", "n": n, "part_bytes": size, "every_read_fails": bool(fail),
+           "form": "small" if rlen <= (16 << 10) else "full", "reply_bytes": n * need, "rounds": rounds, "steps": steps,
+           "device": torch.cuda.get_device_name(0), "parent_lib": os.path.basename(parent_lib)}
+    forms.update(front)
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(forms[k]["measure"](steps))
+    for k in forms:
+        out[k + "_us"] = round(statistics.median(times[k]), 2)
+        out[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    parent = min(out["k_reply_parent_a_us"], out["k_reply_parent_b_us"])
+    out["k_aa_spread_us"] = round(abs(out["k_reply_parent_a_us"] - out["k_reply_parent_b_us"]), 2)
+    out["k_reply_minus_parent_us"] = round(out["k_reply_us"] - parent, 2)
+    out["k_strict_minus_reply_us"] = round(out["k_reply_strict_us"] - out["k_reply_us"], 2)
+    for h in pctx:
+        P.fws_gpu_ctx_destroy(h)
+    ctx.close()
+    return out
+
+
 def c3_stream(target):
     wire, descs, _ = gpu.config_c3(target=target)
     regions = np.zeros(len(descs), dtype=_lib.FRAME_DESC)
@@ -981,9 +1112,21 @@ def main():
     ap.add_argument("--flow-read-kib", type=int, default=16, help="--flow (ii): a read, KiB")
     ap.add_argument("--tx-multi", action="store_true", help="measure fws_gpu_encode_messages_multi (see above)")
     ap.add_argument("--reply", action="store_true", help="measure fws_gpu_reply_messages_multi (see above)")
+    ap.add_argument("--reply-strict", action="store_true",
+                    help="measure fws_gpu_reply_messages_strict against the plain call and the parent's (see above)")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.reply_strict:
+        assert a.parent_lib, "--reply-strict needs --parent-lib"
+        lib = os.path.abspath(a.parent_lib)
+        for n, kib, fail in ((64, 4, False), (512, 4, False), (4096, 4, False), (512, 64, False), (512, 0, True)):
+            lines.append(json.dumps(reply_strict_bench(n, kib << 10, lib, a.rounds, a.steps, fail=fail)))
+            print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.reply:
         assert a.parent_lib, "--reply needs --parent-lib"
         grid_n = "64,512,4096" if a.grid_n == ap.get_default("grid_n") else a.grid_n
