@@ -8,8 +8,9 @@
 // The four phases are k_msg_multi's -- stage the read in LDS, wave 0 walks the
 // header chain and runs the message state machine, the workgroup gathers,
 // unmasks and UTF-8-checks out of LDS, the entries / results / state go out --
-// and nothing reaches global memory before the walk has ended. What the flow
-// form adds:
+// and nothing reaches global memory before the walk has ended; all but the walk
+// are msg_small_common.h's (k_msg_multi calls its gather phase and spells the
+// rest out, see there). What the flow form adds:
 //   * the gather's elements are "the lead, then the frames taken": element 0 is
 //     the payload of the frame in progress that opens the read (source offset 0,
 //     the state's key, which is already rotated to its first byte; length 0 when
@@ -23,17 +24,21 @@
 //     frame_fin; a lead that ends a FIN frame completes the open message there.
 // The UTF-8 regions live in dst byte space, so a cut inside a frame is nothing
 // new to them: the lead belongs to the call's first (seeded) region.
+//
+// The stage's padding covers the windows the lead adds: the lead's windows start
+// at source offset >= 0, a frame that begins inside a dst chunk reaches at most
+// 15 bytes back (the zero chunk in front when its payload starts below 15), and
+// the last window of an element that ends at N starts at or below N - 1 and ends
+// below N + 20 <= 16 * nch + 32.
 #include "fws_device.h"
 #include "fws_internal.h"
+#include "msg_small_common.h"
 
 namespace fwsk {
 
-constexpr uint32_t kMfNone = 0xFFFFFFFFu;
-constexpr uint32_t kMfFrames = kSmallFrames;
+constexpr uint32_t kMfNone = kMsNone;
+constexpr uint32_t kMfFrames = kMsFrames;
 constexpr uint32_t kMfElems = kMfFrames + 1u;   // the lead and the frames
-constexpr uint32_t kMfSeeded = 1u << 16;     // region meta: the carried tail is its left context
-constexpr uint32_t kMfPrefix = 1u << 17;     // region meta: the open part (errors inside it only)
-constexpr uint32_t kMfEntry = 0xFFFFu;       // region meta: its entry
 
 struct MfArgs {
     const uint8_t *wire;
@@ -64,21 +69,9 @@ struct MfHead {
     uint32_t old_tail, old_bad;
 };
 
-__device__ __forceinline__ void mf_refuse(const MfArgs &a, uint32_t r, int32_t status) {
-    fws_decode_result d{};
-    d.status = status;
-    fws_msg_result m{};
-    m.status = status;
-    m.err_frame = kMfNone;
-    m.open_first_frame = kMfNone;
-    gput(a.res + r, d);
-    gput(a.mres + r, m);
-}
-
 template <uint32_t kStage, uint32_t kThreads>
 __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
     constexpr uint32_t kChunks = kStage / 16u;
-    static_assert(kChunks % (4u * kThreads) == 0, "staging rounds of four loads per thread");
     __shared__ u32x4 s_buf[kChunks + 3];            // a zero chunk in front, the read, two zero chunks
     __shared__ fws_frame_info s_fi[kMfFrames];
     __shared__ fws_msg_info s_ent[kMfFrames + 1];   // (a lead that completes a message, then one per frame)
@@ -96,43 +89,15 @@ __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
     const uint32_t tid = threadIdx.x;
     const uint32_t rd = blockIdx.x;
     const fws_msg_read d = a.reads[rd];             // (a uniform address: scalar loads)
-    if ((d.wire_off & 15u) || (d.dst_off & 15u) || d.conn >= a.n_conns) {
-        if (tid == 0) mf_refuse(a, rd, FWS_ERR_INVALID);
+    if (const int32_t bad = ms_check_read(d, a.n_conns, a.max_len, kStage)) {
+        if (tid == 0) ms_refuse(a.res, a.mres, rd, bad);
         return;
     }
     const uint32_t N = d.len;
-    if (N > a.max_len || N > FWS_MSG_MULTI_MAX_READ || N > kStage) {
-        if (tid == 0) mf_refuse(a, rd, FWS_ERR_DECLINED);
-        return;
-    }
-    const uint32_t nch = (N + 15u) >> 4;
-    const uintptr_t base = (uintptr_t)a.wire + d.wire_off;
 
-    // 1. stage: all loads of a thread in flight together (decode_small_wg step 1)
-#pragma unroll
-    for (uint32_t k0 = 0; k0 < kChunks / kThreads; k0 += 4u) {
-        u32x4 v0, v1, v2, v3;
-        const uint32_t c = tid + k0 * kThreads;
-        if (c < nch) v0 = gload16(base + 16u * c);
-        if (c + kThreads < nch) v1 = gload16(base + 16u * (c + kThreads));
-        if (c + 2u * kThreads < nch) v2 = gload16(base + 16u * (c + 2u * kThreads));
-        if (c + 3u * kThreads < nch) v3 = gload16(base + 16u * (c + 3u * kThreads));
-        if (c < nch) s_buf[1u + c] = v0;
-        if (c + kThreads < nch) s_buf[1u + c + kThreads] = v1;
-        if (c + 2u * kThreads < nch) s_buf[1u + c + 2u * kThreads] = v2;
-        if (c + 3u * kThreads < nch) s_buf[1u + c + 3u * kThreads] = v3;
-    }
-    if (tid < 3u) s_buf[tid ? nch + tid : 0u] = u32x4{0u, 0u, 0u, 0u};
-    for (uint32_t i = tid; i < kMfFrames + 2u; i += kThreads) s_rbad[i] = 0u;
-    __syncthreads();
-    // byte 0 of the read; a header window at the last offset and a 20-byte payload
-    // window that starts up to 15 bytes before a payload or ends at N stay in s_buf:
-    // the lead's windows start at source offset >= 0, a frame that begins inside a
-    // dst chunk reaches at most 15 bytes back (the zero chunk in front when its
-    // payload starts below 15), and the last window of an element that ends at N
-    // starts at or below N - 1 and ends below N + 20 <= 16 * nch + 32
-    const uint8_t *sb = (const uint8_t *)(s_buf + 1);
-    static_assert(sizeof(s_buf) >= kStage + 48u, "one chunk in front of the read, two behind");
+    // 1. stage
+    const uint8_t *sb = ms_stage<kChunks, kThreads>(s_buf, (uintptr_t)a.wire + d.wire_off, (N + 15u) >> 4, s_rbad,
+                                                    kMfFrames + 2u, tid);
 
     // 2. the lead, the header chain and the message state machine (wave 0, uniformly)
     if (tid < kWave) {
@@ -165,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
                 m.n_data_frames = 0u; m.opcode = (uint8_t)opc; m.flags = (uint8_t)FWS_MSG_CONTINUED;
                 s_ent[0] = m;
                 s_ereg[0] = opc == 1u ? (uint16_t)0 : (uint16_t)0xFFFFu;
-                if (opc == 1u) { s_rlo[0] = 0u; s_rhi[0] = lead; s_rmeta[0] = 0u | kMfSeeded; }
+                if (opc == 1u) { s_rlo[0] = 0u; s_rhi[0] = lead; s_rmeta[0] = 0u | kMsSeeded; }
             }
             if (opc == 1u) ++nreg;
             ++ne;
@@ -232,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
                                 s_ereg[ne] = opc == 1u ? (uint16_t)nreg : (uint16_t)0xFFFFu;
                                 if (opc == 1u) {
                                     s_rlo[nreg] = db - sb_; s_rhi[nreg] = db;
-                                    s_rmeta[nreg] = ne | (started ? 0u : kMfSeeded);
+                                    s_rmeta[nreg] = ne | (started ? 0u : kMsSeeded);
                                 }
                             }
                             if (opc == 1u) ++nreg;
@@ -287,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
             c.frame_fin = (uint8_t)nff;
             if (open && opc == 1u) {                           // the open TEXT part: the last region
                 s_rlo[nreg] = db - sb_; s_rhi[nreg] = db;
-                s_rmeta[nreg] = kMfEntry | kMfPrefix | (cont ? kMfSeeded : 0u);
+                s_rmeta[nreg] = kMsEntry | kMsPrefix | (cont ? kMsSeeded : 0u);
                 ++nreg;
             }
             s_dpre[np + 1u] = db;
@@ -310,143 +275,26 @@ __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
         }
     }
     __syncthreads();
-    const uint32_t nel = s_h.nel, db = s_h.db, nreg = s_h.nreg;
+    const uint32_t nreg = s_h.nreg;
     const bool over = s_h.over != 0;
-    const uint32_t old_tail = s_h.old_tail;
+    const MsTables t{sb, s_po, s_key, s_dpre, s_cpre, s_rlo, s_rhi, s_rmeta, s_rbad, s_h.nel};
 
     // the frame records (the walk's, whatever the message layer made of them)
     for (uint32_t i = tid; i < s_h.nf; i += kThreads) gput(a.frames + d.frame_base + i, s_fi[i]);
 
-    // the unmasked byte at dst offset y < db; f: an element at or before its owner
-    auto dst_byte = [&](uint32_t y, uint32_t &f) -> uint32_t {
-        while (s_dpre[f + 1u] <= y) ++f;
-        const uint32_t k = y - s_dpre[f];
-        return (uint32_t)sb[s_po[f] + k] ^ ((s_key[f] >> (8u * (k & 3u))) & 0xFFu);
-    };
-    // the owner of dst byte x < db: the last element whose dst prefix is <= x
-    auto owner = [&](uint32_t x) -> uint32_t {
-        uint32_t lo = 0, hi = nel - 1u;
-        while (lo < hi) {
-            const uint32_t m = (lo + hi + 1u) >> 1;
-            if (s_dpre[m] <= x) lo = m; else hi = m - 1u;
-        }
-        return lo;
-    };
-
-    // dst chunk [x0, x0 + 16), zeros from db on: per element that meets it, the 16-B
-    // source window at the chunk's offset in that element -- five aligned dwords from
-    // LDS shifted to the source phase; the window may start up to 15 bytes before
-    // the payload or run past its end, into staged bytes the select drops --, the
-    // key rotated to the chunk's payload phase, the element's bytes selected.
-    auto dst_chunk = [&](uint32_t x0) -> u32x4 {
-        u32x4 v{0u, 0u, 0u, 0u};
-        if (x0 >= db) return v;
-        for (uint32_t f = owner(x0); f < nel && s_dpre[f] < x0 + 16u; ++f) {
-            const uint32_t b = s_dpre[f], e = s_dpre[f + 1u];
-            if (e == b) continue;                            // a control frame, an empty fragment, no lead
-            const uint32_t k = x0 - b;                       // (mod 2^32 when the element starts inside the chunk)
-            const int32_t s = (int32_t)s_po[f] + (int32_t)k; // >= -15
-            const uint32_t sh = (uint32_t)s & 3u;
-            const uint32_t *w = (const uint32_t *)(sb + (s & ~3));
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-            const uint32_t rk = rotr32(s_key[f], 8u * (k & 3u));
-            v.x |= (__builtin_amdgcn_alignbyte(w1, w0, sh) ^ rk) & sel_bytes(x0, b, e);
-            v.y |= (__builtin_amdgcn_alignbyte(w2, w1, sh) ^ rk) & sel_bytes(x0 + 4u, b, e);
-            v.z |= (__builtin_amdgcn_alignbyte(w3, w2, sh) ^ rk) & sel_bytes(x0 + 8u, b, e);
-            v.w |= (__builtin_amdgcn_alignbyte(w4, w3, sh) ^ rk) & sel_bytes(x0 + 12u, b, e);
-        }
-        return v;
-    };
-
-    if (!over) {
-        // 3. gather + unmask, 4. UTF-8 on the chunk in registers. Chunks run to
-        //    db + 3 so an unfinished sequence at the end meets zero bytes. A wave
-        //    takes 64 * steps consecutive chunks: the dword before a lane's chunk is
-        //    its neighbour's last (lane 0: lane 63's of the step before; the wave's
-        //    first chunk: assembled once more).
-        uint8_t *const out = a.dst + d.dst_off;
-        const uint32_t nck = (db + 18u) >> 4;
-        const uint32_t steps = (nck + kThreads - 1u) / kThreads;
-        const uint32_t wlane = tid & (kWave - 1u);
-        uint32_t carry = 0;
-        for (uint32_t st = 0; st < steps; ++st) {            // (the same trips for every lane: the shuffles below)
-            const uint32_t c = ((tid / kWave) * steps + st) * kWave + wlane;
-            const uint32_t x0 = 16u * c;
-            const u32x4 v = c < nck ? dst_chunk(x0) : u32x4{0u, 0u, 0u, 0u};
-            if (c < nck && x0 < db) {
-                if (x0 + 16u <= db) {
-                    gstore16((uintptr_t)out + x0, v);
-                } else {                                     // the last chunk: whole dwords, then bytes
-                    uint32_t j = 0;
-                    for (; x0 + j + 4u <= db; j += 4u) gput(reinterpret_cast<uint32_t *>(out + x0 + j), v[j >> 2]);
-                    for (; x0 + j < db; ++j) gput(out + x0 + j, (uint8_t)(v[j >> 2] >> (8u * (j & 3u))));
-                }
-            }
-            if (!nreg) continue;                             // (uniform)
-            uint32_t prev = __shfl_up(v.w, 1, kWave);
-            if (wlane == 0) prev = carry;
-            carry = __shfl(v.w, kWave - 1, kWave);
-            if (st == 0) {
-                const u32x4 pv = c && c < nck ? dst_chunk(x0 - 16u) : u32x4{0u, 0u, 0u, 0u};
-                if (wlane == 0) prev = pv.w;
-            }
-            if (c >= nck) continue;
-            // ASCII through and through: no region can flag anything here
-            if (!((v.x | v.y | v.z | v.w | (c ? prev : old_tail)) & 0x80808080u)) continue;
-            // the first region with hi + 3 > x0; the regions that meet the chunk follow it
-            uint32_t lo = 0, hi = nreg;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (s_rhi[m] + 3u > x0) hi = m; else lo = m + 1u;
-            }
-            for (uint32_t g = lo; g < nreg && (s_rlo[g] >> 4) <= c; ++g) {
-                const uint32_t rl = s_rlo[g], rh = s_rhi[g], meta = s_rmeta[g];
-                const uint32_t sx = sel_bytes(x0, rl, rh), sy = sel_bytes(x0 + 4u, rl, rh);
-                const uint32_t sz = sel_bytes(x0 + 8u, rl, rh), sw = sel_bytes(x0 + 12u, rl, rh);
-                const uint32_t vx = v.x & sx, vy = v.y & sy, vz = v.z & sz, vw = v.w & sw;
-                const uint32_t p = c ? prev & sel_bytes(x0 - 4u, rl, rh) : ((meta & kMfSeeded) ? old_tail : 0u);
-                if (!((vx | vy | vz | vw | p) & 0x80808080u)) continue;
-                uint32_t bad;
-                if (meta & kMfPrefix)
-                    bad = (utf8_err(vx, p) & sx) | (utf8_err(vy, vx) & sy) | (utf8_err(vz, vy) & sz) |
-                          (utf8_err(vw, vz) & sw);
-                else
-                    bad = utf8_err(vx, p) | utf8_err(vy, vx) | utf8_err(vz, vy) | utf8_err(vw, vz);
-                if (bad) s_rbad[g] = 1u;
-            }
-        }
-        // the control payloads: a wave per control frame taken in
-        uint8_t *const cout = a.ctl + d.ctl_off;
-        const uint32_t lane = tid & (kWave - 1u);
-        for (uint32_t f = tid / kWave; f < nel; f += kThreads / kWave) {
-            const uint32_t co = s_cpre[f], cl = s_cpre[f + 1u] - co;
-            for (uint32_t k = lane; k < cl; k += kWave)
-                gput(cout + co + k, (uint8_t)(sb[s_po[f] + k] ^ (uint8_t)(s_key[f] >> (8u * (k & 3u)))));
-        }
-    }
+    // 3. gather + unmask, 4. UTF-8, the control payloads
+    if (!over) ms_bulk<kThreads>(t, s_h.db, nreg, s_h.old_tail, a.dst + d.dst_off, a.ctl + d.ctl_off, tid);
     __syncthreads();
 
     // the entries with their verdicts, the results, the state
-    for (uint32_t e = tid; e < s_h.ne; e += kThreads) {
-        fws_msg_info m = s_ent[e];
-        const uint32_t g = s_ereg[e];
-        if (!over && g != 0xFFFFu)
-            m.utf8_ok = (s_rbad[g] || ((s_rmeta[g] & kMfSeeded) && s_h.old_bad)) ? (uint8_t)0 : (uint8_t)1;
-        gput(a.msgs + d.msg_base + e, m);
-    }
+    ms_put_entries<kThreads>(t, s_ent, s_ereg, s_h.ne, over, s_h.old_bad, a.msgs + d.msg_base, tid);
     if (tid == 0) {
         if (!over) {
             fws_msg_flow c = s_h.next;
             if (c.msg.open_opcode == 1u) {
-                const uint32_t g = nreg - 1u, rl = s_rlo[g], rh = s_rhi[g];
-                c.msg.utf8_bad = (s_rbad[g] || (s_h.open_cont && s_h.old_bad)) ? 1u : 0u;
-                uint32_t t = s_h.open_cont ? old_tail : 0u;
-                uint32_t k = rh - rl > 3u ? rh - 3u : rl;
-                if (k < rh) {
-                    uint32_t f = owner(k);
-                    for (; k < rh; ++k) t = (t >> 8) | (dst_byte(k, f) << 24);
-                }
-                c.msg.utf8_tail = t & 0xFFFFFF00u;
+                const MsOpenText o = ms_open_text(t, nreg, s_h.open_cont != 0u, s_h.old_tail, s_h.old_bad);
+                c.msg.utf8_bad = o.bad;
+                c.msg.utf8_tail = o.tail;
             }
             gput(a.flows + d.conn, c);
         }

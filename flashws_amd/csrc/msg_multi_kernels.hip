@@ -17,23 +17,26 @@
 // count leaves only its two results, and the byte / entry overflow verdict is
 // known before the first payload byte is stored.
 //
-// UTF-8 is checked on the bytes as they are gathered: the thread that holds a
-// dst chunk in registers takes the dword before it from its neighbour lane, and
-// tests the chunk once per TEXT region that meets it (utf8_err is positional and needs
-// 3 bytes of left context, so chunks are independent). The regions are the
-// completed TEXT entries and the open TEXT part, as in k_utf8_msgs<true>:
-// the carried tail is the left context of a region that began in an earlier
-// call, the open part counts only errors at its own byte positions.
+// The gather / unmask / UTF-8 phase and the control payloads are
+// msg_small_common.h's ms_bulk, shared with k_msg_flow; here an element is a
+// frame. The descriptor checks, the staging and the write-out are spelled out
+// below although the header has them (ms_check_read, ms_stage, ms_put_entries,
+// ms_open_text: k_msg_flow's): with any of the three called from the header the
+// 1024-thread form measured 0.2 to 2.3 us slower at 64 KiB reads, the serial
+// walk's code moving with the register allocation around it (DESIGN.md 4.7.3,
+// "One copy of the shared phases"). A fix to one of them goes into both places.
+// The UTF-8 regions are the completed TEXT entries and the open TEXT part, as in
+// k_utf8_msgs<true>: the carried tail is the left context of a region that
+// began in an earlier call, the open part counts only errors at its own byte
+// positions.
 #include "fws_device.h"
 #include "fws_internal.h"
+#include "msg_small_common.h"
 
 namespace fwsk {
 
-constexpr uint32_t kMmNone = 0xFFFFFFFFu;
-constexpr uint32_t kMmFrames = kSmallFrames;
-constexpr uint32_t kMmSeeded = 1u << 16;     // region meta: the carried tail is its left context
-constexpr uint32_t kMmPrefix = 1u << 17;     // region meta: the open part (errors inside it only)
-constexpr uint32_t kMmEntry = 0xFFFFu;       // region meta: its entry
+constexpr uint32_t kMmNone = kMsNone;
+constexpr uint32_t kMmFrames = kMsFrames;
 
 struct MmArgs {
     const uint8_t *wire;
@@ -65,21 +68,9 @@ struct MmHead {
     uint32_t old_tail, old_bad;
 };
 
-__device__ __forceinline__ void mm_refuse(const MmArgs &a, uint32_t r, int32_t status) {
-    fws_decode_result d{};
-    d.status = status;
-    fws_msg_result m{};
-    m.status = status;
-    m.err_frame = kMmNone;
-    m.open_first_frame = kMmNone;
-    gput(a.res + r, d);
-    gput(a.mres + r, m);
-}
-
 template <uint32_t kStage, uint32_t kThreads>
 __global__ __launch_bounds__(kThreads) void k_msg_multi(MmArgs a) {
     constexpr uint32_t kChunks = kStage / 16u;
-    static_assert(kChunks % (4u * kThreads) == 0, "staging rounds of four loads per thread");
     __shared__ u32x4 s_buf[kChunks + 3];            // a zero chunk in front, the read, two zero chunks
     __shared__ fws_frame_info s_fi[kMmFrames];
     __shared__ fws_msg_info s_ent[kMmFrames];
@@ -97,19 +88,21 @@ __global__ __launch_bounds__(kThreads) void k_msg_multi(MmArgs a) {
     const uint32_t tid = threadIdx.x;
     const uint32_t rd = blockIdx.x;
     const fws_msg_read d = a.reads[rd];             // (a uniform address: scalar loads)
+    // (ms_check_read's text)
     if ((d.wire_off & 15u) || (d.dst_off & 15u) || d.conn >= a.n_conns) {
-        if (tid == 0) mm_refuse(a, rd, FWS_ERR_INVALID);
+        if (tid == 0) ms_refuse(a.res, a.mres, rd, FWS_ERR_INVALID);
+        return;
+    }
+    if (d.len > a.max_len || d.len > FWS_MSG_MULTI_MAX_READ || d.len > kStage) {
+        if (tid == 0) ms_refuse(a.res, a.mres, rd, FWS_ERR_DECLINED);
         return;
     }
     const uint32_t N = d.len;
-    if (N > a.max_len || N > FWS_MSG_MULTI_MAX_READ || N > kStage) {
-        if (tid == 0) mm_refuse(a, rd, FWS_ERR_DECLINED);
-        return;
-    }
     const uint32_t nch = (N + 15u) >> 4;
     const uintptr_t base = (uintptr_t)a.wire + d.wire_off;
 
-    // 1. stage: all loads of a thread in flight together (decode_small_wg step 1)
+    // 1. stage (ms_stage's text): all loads of a thread in flight together
+    static_assert(kChunks % (4u * kThreads) == 0, "staging rounds of four loads per thread");
 #pragma unroll
     for (uint32_t k0 = 0; k0 < kChunks / kThreads; k0 += 4u) {
         u32x4 v0, v1, v2, v3;
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_msg_multi(MmArgs a) {
         if (c + 3u * kThreads < nch) s_buf[1u + c + 3u * kThreads] = v3;
     }
     if (tid < 3u) s_buf[tid ? nch + tid : 0u] = u32x4{0u, 0u, 0u, 0u};
-    for (uint32_t i = tid; i <= kMmFrames; i += kThreads) s_rbad[i] = 0u;
+    for (uint32_t i = tid; i <= kMsFrames; i += kThreads) s_rbad[i] = 0u;
     __syncthreads();
     // byte 0 of the read; a header window at the last offset and a 20-byte payload
     // window that starts up to 15 bytes before a payload or ends at N stay in s_buf
@@ -204,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_msg_multi(MmArgs a) {
                             s_ereg[ne] = opc == 1u ? (uint16_t)nreg : (uint16_t)0xFFFFu;
                             if (opc == 1u) {
                                 s_rlo[nreg] = db - sb_; s_rhi[nreg] = db;
-                                s_rmeta[nreg] = ne | (started ? 0u : kMmSeeded);
+                                s_rmeta[nreg] = ne | (started ? 0u : kMsSeeded);
                             }
                         }
                         if (opc == 1u) ++nreg;
@@ -256,7 +249,7 @@ __global__ __launch_bounds__(kThreads) void k_msg_multi(MmArgs a) {
                 c.n_msgs = old.n_msgs + ne;
                 if (open && opc == 1u) {                       // the open TEXT part: the last region
                     s_rlo[nreg] = db - sb_; s_rhi[nreg] = db;
-                    s_rmeta[nreg] = kMmEntry | kMmPrefix | (cont ? kMmSeeded : 0u);
+                    s_rmeta[nreg] = kMsEntry | kMsPrefix | (cont ? kMsSeeded : 0u);
                     ++nreg;
                 }
                 s_dpre[np] = db;
@@ -280,131 +273,26 @@ __global__ __launch_bounds__(kThreads) void k_msg_multi(MmArgs a) {
     }
     __syncthreads();
     if (s_h.mode) {
-        if (tid == 0) mm_refuse(a, rd, (int32_t)s_h.mode);
+        if (tid == 0) ms_refuse(a.res, a.mres, rd, (int32_t)s_h.mode);
         return;
     }
-    const uint32_t np = s_h.np, db = s_h.db, nreg = s_h.nreg;
+    const uint32_t nreg = s_h.nreg;
     const bool over = s_h.over != 0;
-    const uint32_t old_tail = s_h.old_tail;
+    const MsTables t{sb, s_po, s_key, s_dpre, s_cpre, s_rlo, s_rhi, s_rmeta, s_rbad, s_h.np};
 
     // the frame records (the walk's, whatever the message layer made of them)
     for (uint32_t i = tid; i < s_h.nf; i += kThreads) gput(a.frames + d.frame_base + i, s_fi[i]);
 
-    // the unmasked byte at dst offset y < db; f: a frame at or before its owner
-    auto dst_byte = [&](uint32_t y, uint32_t &f) -> uint32_t {
-        while (s_dpre[f + 1u] <= y) ++f;
-        const uint32_t k = y - s_dpre[f];
-        return (uint32_t)sb[s_po[f] + k] ^ ((s_key[f] >> (8u * (k & 3u))) & 0xFFu);
-    };
-    // the owner of dst byte x < db: the last frame whose dst prefix is <= x
-    auto owner = [&](uint32_t x) -> uint32_t {
-        uint32_t lo = 0, hi = np - 1u;
-        while (lo < hi) {
-            const uint32_t m = (lo + hi + 1u) >> 1;
-            if (s_dpre[m] <= x) lo = m; else hi = m - 1u;
-        }
-        return lo;
-    };
-
-    // dst chunk [x0, x0 + 16), zeros from db on: per frame that meets it, the 16-B
-    // source window at the chunk's offset in that frame -- five aligned dwords from
-    // LDS shifted to the source phase; the window may start up to 15 bytes before
-    // the payload or run past its end, into staged bytes the select drops --, the
-    // key rotated to the chunk's payload phase, the frame's bytes selected.
-    auto dst_chunk = [&](uint32_t x0) -> u32x4 {
-        u32x4 v{0u, 0u, 0u, 0u};
-        if (x0 >= db) return v;
-        for (uint32_t f = owner(x0); f < np && s_dpre[f] < x0 + 16u; ++f) {
-            const uint32_t b = s_dpre[f], e = s_dpre[f + 1u];
-            if (e == b) continue;                            // a control frame or an empty fragment
-            const uint32_t k = x0 - b;                       // (mod 2^32 when the frame starts inside the chunk)
-            const int32_t s = (int32_t)s_po[f] + (int32_t)k; // >= -15
-            const uint32_t sh = (uint32_t)s & 3u;
-            const uint32_t *w = (const uint32_t *)(sb + (s & ~3));
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-            const uint32_t rk = rotr32(s_key[f], 8u * (k & 3u));
-            v.x |= (__builtin_amdgcn_alignbyte(w1, w0, sh) ^ rk) & sel_bytes(x0, b, e);
-            v.y |= (__builtin_amdgcn_alignbyte(w2, w1, sh) ^ rk) & sel_bytes(x0 + 4u, b, e);
-            v.z |= (__builtin_amdgcn_alignbyte(w3, w2, sh) ^ rk) & sel_bytes(x0 + 8u, b, e);
-            v.w |= (__builtin_amdgcn_alignbyte(w4, w3, sh) ^ rk) & sel_bytes(x0 + 12u, b, e);
-        }
-        return v;
-    };
-
-    if (!over) {
-        // 3. gather + unmask, 4. UTF-8 on the chunk in registers. Chunks run to
-        //    db + 3 so an unfinished sequence at the end meets zero bytes. A wave
-        //    takes 64 * steps consecutive chunks: the dword before a lane's chunk is
-        //    its neighbour's last (lane 0: lane 63's of the step before; the wave's
-        //    first chunk: assembled once more).
-        uint8_t *const out = a.dst + d.dst_off;
-        const uint32_t nck = (db + 18u) >> 4;
-        const uint32_t steps = (nck + kThreads - 1u) / kThreads;
-        const uint32_t wlane = tid & (kWave - 1u);
-        uint32_t carry = 0;
-        for (uint32_t st = 0; st < steps; ++st) {            // (the same trips for every lane: the shuffles below)
-            const uint32_t c = ((tid / kWave) * steps + st) * kWave + wlane;
-            const uint32_t x0 = 16u * c;
-            const u32x4 v = c < nck ? dst_chunk(x0) : u32x4{0u, 0u, 0u, 0u};
-            if (c < nck && x0 < db) {
-                if (x0 + 16u <= db) {
-                    gstore16((uintptr_t)out + x0, v);
-                } else {                                     // the last chunk: whole dwords, then bytes
-                    uint32_t j = 0;
-                    for (; x0 + j + 4u <= db; j += 4u) gput(reinterpret_cast<uint32_t *>(out + x0 + j), v[j >> 2]);
-                    for (; x0 + j < db; ++j) gput(out + x0 + j, (uint8_t)(v[j >> 2] >> (8u * (j & 3u))));
-                }
-            }
-            if (!nreg) continue;                             // (uniform)
-            uint32_t prev = __shfl_up(v.w, 1, kWave);
-            if (wlane == 0) prev = carry;
-            carry = __shfl(v.w, kWave - 1, kWave);
-            if (st == 0) {
-                const u32x4 pv = c && c < nck ? dst_chunk(x0 - 16u) : u32x4{0u, 0u, 0u, 0u};
-                if (wlane == 0) prev = pv.w;
-            }
-            if (c >= nck) continue;
-            // ASCII through and through: no region can flag anything here
-            if (!((v.x | v.y | v.z | v.w | (c ? prev : old_tail)) & 0x80808080u)) continue;
-            // the first region with hi + 3 > x0; the regions that meet the chunk follow it
-            uint32_t lo = 0, hi = nreg;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (s_rhi[m] + 3u > x0) hi = m; else lo = m + 1u;
-            }
-            for (uint32_t g = lo; g < nreg && (s_rlo[g] >> 4) <= c; ++g) {
-                const uint32_t rl = s_rlo[g], rh = s_rhi[g], meta = s_rmeta[g];
-                const uint32_t sx = sel_bytes(x0, rl, rh), sy = sel_bytes(x0 + 4u, rl, rh);
-                const uint32_t sz = sel_bytes(x0 + 8u, rl, rh), sw = sel_bytes(x0 + 12u, rl, rh);
-                const uint32_t vx = v.x & sx, vy = v.y & sy, vz = v.z & sz, vw = v.w & sw;
-                const uint32_t p = c ? prev & sel_bytes(x0 - 4u, rl, rh) : ((meta & kMmSeeded) ? old_tail : 0u);
-                if (!((vx | vy | vz | vw | p) & 0x80808080u)) continue;
-                uint32_t bad;
-                if (meta & kMmPrefix)
-                    bad = (utf8_err(vx, p) & sx) | (utf8_err(vy, vx) & sy) | (utf8_err(vz, vy) & sz) |
-                          (utf8_err(vw, vz) & sw);
-                else
-                    bad = utf8_err(vx, p) | utf8_err(vy, vx) | utf8_err(vz, vy) | utf8_err(vw, vz);
-                if (bad) s_rbad[g] = 1u;
-            }
-        }
-        // the control payloads: a wave per control frame taken in
-        uint8_t *const cout = a.ctl + d.ctl_off;
-        const uint32_t lane = tid & (kWave - 1u);
-        for (uint32_t f = tid / kWave; f < np; f += kThreads / kWave) {
-            const uint32_t co = s_cpre[f], cl = s_cpre[f + 1u] - co;
-            for (uint32_t k = lane; k < cl; k += kWave)
-                gput(cout + co + k, (uint8_t)(sb[s_po[f] + k] ^ (uint8_t)(s_key[f] >> (8u * (k & 3u)))));
-        }
-    }
+    // 3. gather + unmask, 4. UTF-8, the control payloads
+    if (!over) ms_bulk<kThreads>(t, s_h.db, nreg, s_h.old_tail, a.dst + d.dst_off, a.ctl + d.ctl_off, tid);
     __syncthreads();
 
-    // the entries with their verdicts, the results, the carry
+    // the entries with their verdicts (ms_put_entries' text), the results, the carry (ms_open_text's text)
     for (uint32_t e = tid; e < s_h.ne; e += kThreads) {
         fws_msg_info m = s_ent[e];
         const uint32_t g = s_ereg[e];
         if (!over && g != 0xFFFFu)
-            m.utf8_ok = (s_rbad[g] || ((s_rmeta[g] & kMmSeeded) && s_h.old_bad)) ? (uint8_t)0 : (uint8_t)1;
+            m.utf8_ok = (s_rbad[g] || ((s_rmeta[g] & kMsSeeded) && s_h.old_bad)) ? (uint8_t)0 : (uint8_t)1;
         gput(a.msgs + d.msg_base + e, m);
     }
     if (tid == 0) {
@@ -413,13 +301,13 @@ __global__ __launch_bounds__(kThreads) void k_msg_multi(MmArgs a) {
             if (c.open_opcode == 1u) {
                 const uint32_t g = nreg - 1u, rl = s_rlo[g], rh = s_rhi[g];
                 c.utf8_bad = (s_rbad[g] || (s_h.open_cont && s_h.old_bad)) ? 1u : 0u;
-                uint32_t t = s_h.open_cont ? old_tail : 0u;
+                uint32_t tl = s_h.open_cont ? s_h.old_tail : 0u;
                 uint32_t k = rh - rl > 3u ? rh - 3u : rl;
                 if (k < rh) {
-                    uint32_t f = owner(k);
-                    for (; k < rh; ++k) t = (t >> 8) | (dst_byte(k, f) << 24);
+                    uint32_t f = ms_owner(t, k);
+                    for (; k < rh; ++k) tl = (tl >> 8) | (ms_dst_byte(t, k, f) << 24);
                 }
-                c.utf8_tail = t & 0xFFFFFF00u;
+                c.utf8_tail = tl & 0xFFFFFF00u;
             }
             gput(a.carries + d.conn, c);
         }

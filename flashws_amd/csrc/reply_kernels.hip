@@ -23,13 +23,10 @@
 //
 // Bytes: the region is written as 16-B chunks from its aligned start, a wave
 // taking one 4 KiB unit per round as in k_tx_multi. The frames are irregular, so
-// a chunk finds its frame by a binary search in the table's offsets. A chunk
-// inside one payload is two aligned source loads shifted by the source
-// misalignment; a chunk that meets a header or the region's end (a seam) ORs,
-// for every frame that meets it, the header from registers and the source
-// window, each selected on its byte range (tx_multi_common.h). The region's last
-// chunk is stored bytewise up to out_len: no byte outside
-// [out_off, out_off + out_len) is written.
+// a chunk finds its frame by a binary search in the table's offsets
+// (rp_write_bytes, reply_common.h, shared with k_reply_strict as the scan and
+// the frame records are). The region's last chunk is stored bytewise up to
+// out_len: no byte outside [out_off, out_off + out_len) is written.
 #include "fws_device.h"
 #include "fws_internal.h"
 #include "reply_common.h"
@@ -52,16 +49,6 @@ struct RpArgs {
     uint32_t n_conns;
     uint32_t flags;
 };
-
-__device__ __forceinline__ void rp_result(const RpArgs &a, uint32_t r, int32_t status, uint32_t n_frames,
-                                          uint64_t out_len, uint32_t lmnf) {
-    fws_tx_result x{};
-    x.status = status;
-    x.n_frames = n_frames;
-    x.out_len = out_len;
-    x.last_msg_not_fin = lmnf;
-    gput(a.res + r, x);
-}
 
 template <uint32_t kThreads>
 __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
 
     // ---- what the descriptors alone decide
     if ((g.out_off & 15u) || d.conn >= a.n_conns) {
-        if (tid == 0) rp_result(a, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
+        if (tid == 0) rp_result(a.res, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
         return;
     }
     fws_tx_conn *const conn = a.conns + d.conn;
@@ -95,11 +82,11 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
     const bool undelivered = mr.status == FWS_ERR_DECLINED || mr.status == FWS_ERR_INVALID ||
                              mr.n_msgs > d.msg_cap || mr.data_bytes > d.dst_cap || mr.ctl_bytes > d.ctl_cap;
     if (!undelivered && mr.n_msgs > FWS_MSG_MULTI_MAX_FRAMES + 1u) {   // not a decode output
-        if (tid == 0) rp_result(a, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
+        if (tid == 0) rp_result(a.res, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
         return;
     }
     if (undelivered) {                                 // nothing to answer
-        if (tid == 0) rp_result(a, rd, 0, 0u, 0u, conn->last_msg_not_fin != 0u ? 1u : 0u);
+        if (tid == 0) rp_result(a.res, rd, 0, 0u, 0u, conn->last_msg_not_fin != 0u ? 1u : 0u);
         return;
     }
 
@@ -161,11 +148,11 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
     }
     __syncthreads();
     if (close_sent != 0u) {                            // nothing more to say
-        if (tid == 0) rp_result(a, rd, 0, 0u, 0u, open);
+        if (tid == 0) rp_result(a.res, rd, 0, 0u, 0u, open);
         return;
     }
     if (s_bad) {                                       // not a decode output
-        if (tid == 0) rp_result(a, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
+        if (tid == 0) rp_result(a.res, rd, FWS_ERR_INVALID, 0u, 0u, 0u);
         return;
     }
     const uint32_t fc = s_first_close, fd = s_first_data;
@@ -178,20 +165,9 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
         if (kind[k]) cnt += 1u, byt += tm_hdr_len(len[k], false) + len[k];
     }
     const uint32_t lane = tid & 63u, wv = tid >> 6;
-    uint32_t ic = cnt, ib = byt;                       // inclusive over the wave
-#pragma unroll
-    for (uint32_t s = 1u; s < 64u; s <<= 1) {
-        const uint32_t c2 = __shfl_up(ic, s), b2 = __shfl_up(ib, s);
-        if (lane >= s) ic += c2, ib += b2;
-    }
-    if (lane == 63u) s_wc[wv] = ic, s_wb[wv] = ib;
-    __syncthreads();
-    uint32_t pc = ic - cnt, pb = ib - byt, nf = 0u, total = 0u;
-#pragma unroll
-    for (uint32_t w = 0; w < kWaves; ++w) {
-        if (w < wv) pc += s_wc[w], pb += s_wb[w];
-        nf += s_wc[w], total += s_wb[w];               // <= 258 * (128 KiB + 10)
-    }
+    const RpScan sc = rp_scan<kWaves>(cnt, byt, s_wc, s_wb, lane, wv);
+    const uint32_t nf = sc.nf, total = sc.total;
+    uint32_t pc = sc.pc, pb = sc.pb;
 #pragma unroll
     for (uint32_t k = 0; k < kIpt; ++k) {
         if (!kind[k]) continue;
@@ -211,76 +187,19 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
 
     // ---- the verdict on the region
     if (total > g.out_cap) {
-        if (tid == 0) rp_result(a, rd, FWS_ERR_CAPACITY, nf, total, 0u);
+        if (tid == 0) rp_result(a.res, rd, FWS_ERR_CAPACITY, nf, total, 0u);
         return;
     }
 
-    // ---- the bytes (k_tx_multi's mapping: a wave's round is one 4 KiB unit, lane chunks 1 KiB apart)
-    uint8_t *const R = a.out + g.out_off;
-    const uint32_t nch = (total + 15u) >> 4;
-    const uint32_t lane0 = wv * (64u * kTmU) + lane;
-    for (uint32_t r0 = 0; r0 < nch; r0 += kThreads * kTmU) {   // (uniform trip count)
-        const uint32_t c0 = r0 + lane0;
-        uintptr_t sb[kTmU];
-        uint32_t sh[kTmU], fj[kTmU];
-        uint32_t full = 0, seam = 0;
-#pragma unroll
-        for (uint32_t u = 0; u < kTmU; ++u) {
-            const uint32_t c = c0 + u * 64u, av = c < nch ? c * 16u : 0u;
-            const uint32_t j = nf > 1u ? rp_frame_of(s_t, nf, av) : 0u;
-            fj[u] = j;
-            const uint32_t P = s_t.off[j] + (s_t.bh[j] >> 8), E = P + s_t.len[j];
-            const bool in = c < nch && av >= P && av + 16u <= E;
-            if (in) full |= 1u << u;
-            else if (c < nch) seam |= 1u << u;
-            const uintptr_t sa = (uintptr_t)s_t.src[j] + (uintptr_t)(av - P);
-            sb[u] = sa & ~uintptr_t(15);
-            sh[u] = (uint32_t)(sa & 15u);
-        }
-        u32x4 v0[kTmU], v1[kTmU];
-#pragma unroll
-        for (uint32_t u = 0; u < kTmU; ++u) {
-            if ((full >> u) & 1u) {
-                v0[u] = gload16<false>(sb[u]);
-                v1[u] = gload16<false>(sh[u] ? sb[u] + 16u : sb[u]);
-            } else {
-                v0[u] = v1[u] = u32x4{0u, 0u, 0u, 0u};
-            }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < kTmU; ++u)
-            if ((full >> u) & 1u)
-                gstore16<true>((uintptr_t)(R + (c0 + u * 64u) * 16u), tm_shr_bytes(v0[u], v1[u], sh[u]));
-        if (seam) {
-#pragma unroll
-            for (uint32_t u = 0; u < kTmU; ++u) {
-                if (!((seam >> u) & 1u)) continue;
-                const uint32_t av = (c0 + u * 64u) * 16u;
-                tm_store_chunk(R, av, total, rp_seam_chunk(s_t, nf, av, fj[u]));
-            }
-        }
-    }
-
-    // ---- the frame records
-    const uint32_t nrec = nf < g.frame_cap ? nf : g.frame_cap;
-    for (uint32_t j = tid; j < nrec; j += kThreads) {
-        const TmFrame f = rp_frame(s_t, j);
-        fws_frame_info fi;
-        fi.hdr_off = f.O;
-        fi.payload_len = f.plen;
-        fi.key = 0u;
-        fi.opcode = (uint8_t)(f.b0 & 15u);
-        fi.fin = (uint8_t)(f.b0 >> 7);
-        fi.hdr_len = (uint8_t)f.hlen;
-        fi.flags = 0;
-        gput(a.frames + g.frame_base + j, fi);
-    }
+    // ---- the bytes, the frame records
+    rp_write_bytes<kThreads>(s_t, nf, total, a.out + g.out_off, lane, wv);
+    rp_put_records<kThreads>(s_t, nf < g.frame_cap ? nf : g.frame_cap, a.frames + g.frame_base, tid);
 
     // ---- the result and both states, last
     if (tid == 0) {
         // the open part, when it is sent, is the last data frame and leaves its message open; any other ends one
         const uint32_t next_open = fd < fc ? ((s_open_item && fc == kRpNone) ? 1u : 0u) : open;
-        rp_result(a, rd, 0, nf, total, next_open);
+        rp_result(a.res, rd, 0, nf, total, next_open);
         conn->last_msg_not_fin = next_open;
         conn->frames += nf;
         conn->wire_bytes += total;

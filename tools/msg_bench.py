@@ -45,6 +45,7 @@ after 64 distinct ones. One JSON line per grid point.
        the multi call of a library built from the parent commit (--parent-lib),
        two contexts of which give the A/A spread; the forms alternate within
        every round, and every form's outputs are compared byte for byte first.
+       A parent library that has the flow call gives it a second A/A pair.
   (ii) flow_frames  n connections each receive one 1 MiB frame in 16 KiB reads:
        the flow protocol (every read uploaded once, one launch per step for all
        connections) against the only alternative today, the frame kept on the
@@ -75,6 +76,8 @@ up to 16 KiB. One JSON line per grid point.
        one-frame sends of the same payloads (4 KiB and 64 KiB parts); the parent
        form runs twice per round for its own spread, and the reply launch once
        more with flags 0 (the entries, the scan and the table, no frame).
+       A parent library that has the reply call is timed on it too, in both
+       contexts, after its output was compared with this tree's.
 The forms alternate within every round; both paths' output bytes are compared
 first. One JSON line per grid point.
 usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out FILE]
@@ -90,8 +93,9 @@ x 64 KiB, and one row where every read is a CLOSE of one byte and fails. HIP
 events around back-to-back launches through raw pointers; within each round,
 alternating: this tree's fws_gpu_reply_messages_multi, the same call of a
 library built from the parent commit in two contexts (the A/A spread), and the
-strict call. Every form's output is compared byte for byte first. SO is the
-parent commit's library (it has the plain call and lacks the strict one).
+strict call -- and the parent's strict call in both contexts where it has one.
+Every form's output is compared byte for byte first. SO is the parent commit's
+library.
        python tools/msg_bench.py --reply-strict --parent-lib SO [--rounds R] [--steps S] [--out FILE]"""
 import argparse
 import ctypes as C
@@ -469,7 +473,7 @@ def flow_cost(n, size, parent_lib, rounds, steps):
     for name, res_t, args in _lib.SIGNATURES:
         if hasattr(P, name):
             getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
-    assert not hasattr(P, "fws_gpu_decode_messages_flow"), "--parent-lib is this tree's library"
+    parent_has_flow = hasattr(P, "fws_gpu_decode_messages_flow")
     rng = np.random.default_rng(1000 * n + size)
     distinct = [multi_read(rng, size) for _ in range(min(n, 64))]
     cap = max(f for _, f in distinct) + 4
@@ -494,27 +498,26 @@ def flow_cost(n, size, parent_lib, rounds, steps):
         assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0
         pctx.append(h)
 
-    def parent(h):
+    def parent(h, fn=P.fws_gpu_decode_messages_multi, state=carries):
         def f(i):
-            assert P.fws_gpu_decode_messages_multi(h, wire.data_ptr(), reads.data_ptr(), n, size, frames.data_ptr(),
-                                                   msgs.data_ptr(), dst.data_ptr(), ctl.data_ptr(), res.data_ptr(),
-                                                   mres.data_ptr(), carries.data_ptr(), n, s.cuda_stream) == 0
+            assert fn(h, wire.data_ptr(), reads.data_ptr(), n, size, frames.data_ptr(), msgs.data_ptr(), dst.data_ptr(),
+                      ctl.data_ptr(), res.data_ptr(), mres.data_ptr(), state.data_ptr(), n, s.cuda_stream) == 0
         return f
 
-    def f_multi(i):
-        assert gpu.decode_messages_multi(ctx, wire, reads, n, size, frames, msgs, dst, ctl, res, mres, carries, n) == 0
-
-    def f_flow(i):
-        assert gpu.decode_messages_flow(ctx, wire, reads, n, size, frames, msgs, dst, ctl, res, mres, flows, n) == 0
-
-    forms = {"parent_a": parent(pctx[0]), "parent_b": parent(pctx[1]), "multi": f_multi, "flow": f_flow}
+    # (this tree's calls through raw pointers as the parent's: at n = 1 the Python wrapper's argument conversion
+    # showed as 0.2 us on a kernel that was the parent's)
+    forms = {"parent_a": parent(pctx[0]), "parent_b": parent(pctx[1]),
+             "multi": parent(ctx.h, _lib.lib().fws_gpu_decode_messages_multi),
+             "flow": parent(ctx.h, _lib.lib().fws_gpu_decode_messages_flow, flows)}
+    if parent_has_flow:                               # the parent's flow call, its own A/A pair
+        forms.update({"flow_parent_" + x: parent(h, P.fws_gpu_decode_messages_flow, flows) for x, h in zip("ab", pctx)})
     want = None
     for k, f in forms.items():                        # checked first: every form writes the same bytes
         for t in (dst, ctl, frames, msgs, res, mres, carries, flows):
             t.zero_()
         f(0)
         torch.cuda.synchronize()
-        state = flows.view(n, -1)[:, :64].reshape(-1) if k == "flow" else carries
+        state = flows.view(n, -1)[:, :64].reshape(-1) if k.startswith("flow") else carries
         got = [t.clone() for t in (dst, ctl, frames, msgs, res, mres, state)]
         want = want or got
         assert all(torch.equal(a, b) for a, b in zip(got, want)), k
@@ -534,6 +537,9 @@ def flow_cost(n, size, parent_lib, rounds, steps):
     out["aa_spread_us"] = round(abs(out["parent_a_us"] - out["parent_b_us"]), 2)
     out["flow_minus_parent_us"] = round(out["flow_us"] - base, 2)
     out["multi_minus_parent_us"] = round(out["multi_us"] - base, 2)
+    if parent_has_flow:
+        out["flow_aa_spread_us"] = round(abs(out["flow_parent_a_us"] - out["flow_parent_b_us"]), 2)
+        out["flow_minus_flow_parent_us"] = round(out["flow_us"] - min(out["flow_parent_a_us"], out["flow_parent_b_us"]), 2)
     for h in pctx:
         P.fws_gpu_ctx_destroy(h)
     ctx.close()
@@ -750,7 +756,7 @@ def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
     for name, res_t, args in _lib.SIGNATURES:
         if hasattr(P, name):
             getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
-    assert not hasattr(P, "fws_gpu_reply_messages_multi"), "--parent-lib is this tree's library"
+    parent_has_reply = hasattr(P, "fws_gpu_reply_messages_multi")
     rng = np.random.default_rng(31 * n + size)
     hdr = [header(2, 1, size, int(rng.integers(0, 1 << 32))) for _ in range(min(n, 64))]
     rlen = len(hdr[0]) + size
@@ -832,9 +838,9 @@ def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
     reply_fn = _lib.lib().fws_gpu_reply_messages_multi
     rp = [t.data_ptr() for t in (reads, msgs, dst, ctl, mres, d_regions, out_new, tres, conns_new, states)]
 
-    def f_reply(i, flags=_lib.FWS_REPLY_CONTROL | _lib.FWS_REPLY_ECHO):
-        assert reply_fn(ctx.h, rp[0], n, max_len, rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], None, rp[7], rp[8],
-                        rp[9], n, flags, s.cuda_stream) == 0
+    def f_reply(i, flags=_lib.FWS_REPLY_CONTROL | _lib.FWS_REPLY_ECHO, fn=reply_fn, h=None, out=rp[6], conns=rp[8]):
+        assert fn(h or ctx.h, rp[0], n, max_len, rp[1], rp[2], rp[3], rp[4], rp[5], out, None, rp[7], conns,
+                  rp[9], n, flags, s.cuda_stream) == 0
 
     decode_fn = _lib.lib().fws_gpu_decode_messages_flow
     dp = [t.data_ptr() for t in (wire, reads, frames, msgs, dst, ctl, res, mres, flows)]
@@ -852,6 +858,11 @@ def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
     assert (t["status"] == 0).all() and (t["out_len"] == need).all() and (t["n_frames"] == 1).all()
     assert torch.equal(out_new, out_old) and int(out_new.view(n, oslot)[:, 0].min()) == 0x82
     assert torch.equal(conns_new, conns_old)
+    if parent_has_reply:                              # and the parent's reply call, into the old path's buffers
+        for h in pctx:
+            out_old.zero_(), conns_old.zero_()
+            f_reply(0, fn=P.fws_gpu_reply_messages_multi, h=h, out=out_old.data_ptr(), conns=conns_old.data_ptr())
+            assert torch.equal(out_new, out_old) and torch.equal(conns_new, conns_old)
     out = {"measure": "reply", "n": n, "part_bytes": size, "form": "small" if rlen <= (16 << 10) else "full",
            "reply_bytes": n * need, "rounds": rounds, "steps": steps, "device": torch.cuda.get_device_name(0),
            "parent_lib": os.path.basename(parent_lib)}
@@ -863,6 +874,9 @@ def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
                   "k_reply": (timed, f_reply),
                   # flags 0: the entries read, the scan and the table, no frame (where the time of a small call goes)
                   "k_reply_no_frames": (timed, lambda i: f_reply(i, 0))})
+    if parent_has_reply:                              # the timed launches of all three write into one set of buffers
+        forms.update({"k_reply_parent_" + x: (timed, lambda i, h=h: f_reply(i, fn=P.fws_gpu_reply_messages_multi, h=h))
+                      for x, h in zip("ab", pctx)})
     times = {k: [] for k in forms}
     for rnd in range(rounds):
         for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
@@ -878,6 +892,10 @@ def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
     out["k_aa_spread_us"] = round(abs(out["k_tx_multi_a_us"] - out["k_tx_multi_b_us"]), 2)
     out["k_reply_over_tx_multi"] = round(out["k_reply_us"] / kb, 3)
     out["k_reply_gb_s"] = round(n * need / out["k_reply_us"] / 1e3, 2)
+    if parent_has_reply:
+        out["k_reply_aa_spread_us"] = round(abs(out["k_reply_parent_a_us"] - out["k_reply_parent_b_us"]), 2)
+        out["k_reply_minus_parent_us"] = round(out["k_reply_us"] - min(out["k_reply_parent_a_us"],
+                                                                        out["k_reply_parent_b_us"]), 2)
     for h in pctx:
         P.fws_gpu_ctx_destroy(h)
     ctx.close()
@@ -893,8 +911,8 @@ def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
     for name, res_t, args in _lib.SIGNATURES:
         if hasattr(P, name):
             getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
-    assert hasattr(P, "fws_gpu_reply_messages_multi") and not hasattr(P, "fws_gpu_reply_messages_strict"), \
-        "--parent-lib is not the parent commit's library"
+    assert hasattr(P, "fws_gpu_reply_messages_multi"), "--parent-lib has no plain reply call"
+    parent_has_strict = hasattr(P, "fws_gpu_reply_messages_strict")
     if fail:
         size = 1
     rng = np.random.default_rng(37 * n + size)
@@ -967,6 +985,8 @@ def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
              "k_reply_parent_a": form(P.fws_gpu_reply_messages_multi, pctx[0], False),
              "k_reply_parent_b": form(P.fws_gpu_reply_messages_multi, pctx[1], False),
              "k_reply_strict": form(L.fws_gpu_reply_messages_strict, ctx.h, True)}
+    strict_parents = ("k_reply_strict_parent_a", "k_reply_strict_parent_b") if parent_has_strict else ()
+    forms.update({k: form(P.fws_gpu_reply_messages_strict, h, True) for k, h in zip(strict_parents, pctx)})
     # flags 0: the entries read, the minima, the scan and the table, no frame unless a read fails
     front = {"k_reply_no_frames": form(L.fws_gpu_reply_messages_multi, ctx.h, False, 0),
              "k_reply_strict_no_frames": form(L.fws_gpu_reply_messages_strict, ctx.h, True, 0)}
@@ -978,6 +998,8 @@ def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
     a, st = forms["k_reply"], np.frombuffer(states[:ssz].cpu().numpy().tobytes(), dtype=_lib.REPLY_STATE)
     for k in ("k_reply_parent_a", "k_reply_parent_b") + (() if fail else ("k_reply_strict",)):
         assert all(torch.equal(a[x], forms[k][x]) for x in ("out", "res", "conns")), k
+    for k in strict_parents:
+        assert all(torch.equal(forms["k_reply_strict"][x], forms[k][x]) for x in ("out", "res", "conns")), k
     t = np.frombuffer(forms["k_reply_strict"]["res"].cpu().numpy().tobytes(), dtype=_lib.TX_RESULT)
     assert (t["status"] == 0).all() and (t["out_len"] == need).all() and (t["n_frames"] == 1).all()
     assert (st["fail_code"] == (1002 if fail else 0)).all() and (st["close_sent"] == int(fail)).all()
@@ -999,6 +1021,10 @@ def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
     out["k_aa_spread_us"] = round(abs(out["k_reply_parent_a_us"] - out["k_reply_parent_b_us"]), 2)
     out["k_reply_minus_parent_us"] = round(out["k_reply_us"] - parent, 2)
     out["k_strict_minus_reply_us"] = round(out["k_reply_strict_us"] - out["k_reply_us"], 2)
+    if parent_has_strict:
+        sp = [out[k + "_us"] for k in strict_parents]
+        out["k_strict_aa_spread_us"] = round(abs(sp[0] - sp[1]), 2)
+        out["k_strict_minus_parent_us"] = round(out["k_reply_strict_us"] - min(sp), 2)
     for h in pctx:
         P.fws_gpu_ctx_destroy(h)
     ctx.close()
