@@ -161,6 +161,7 @@ SIGNATURES = [
     ("fws_gpu_decode_messages_carry", _I, [_P, _P, _U64, _P, _U32, _P, _U32, _P, _U64, _P, _U64, _P, _P, _P, _P]),
     ("fws_gpu_decode_messages_multi", _I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P]),
     ("fws_gpu_decode_messages_flow", _I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P]),
+    ("fws_gpu_decode_messages_flow_client", _I, [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _U32, _P]),
     ("fws_gpu_validate_utf8", _I, [_P, _P, _P, _U32, _P, _P]),
     ("fws_rx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_rx_session_destroy", None, [_P]),
@@ -187,6 +188,10 @@ SIGNATURES = [
                                           _P]),
     ("fws_gpu_reply_messages_strict", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P, _P, _P,
                                            _U32, _U32, _P]),
+    ("fws_gpu_reply_messages_multi_client", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _U32,
+                                                 _P, _P]),
+    ("fws_gpu_reply_messages_strict_client", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P,
+                                                  _P, _P, _U32, _U32, _P, _P]),
     ("fws_tx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_tx_session_destroy", None, [_P]),
     ("fws_tx_session_send", _I, [_P, _P, _P, _P, _P, _P, _U32, _P, _U64, _PU64]),

@@ -483,10 +483,11 @@ int fws_gpu_decode_messages_multi(fws_gpu_ctx *ctx, const void *dev_wire, const 
                                 n_conns, (hipStream_t)stream);
 }
 
-int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire, const fws_msg_read *dev_reads, uint32_t n,
-                                 uint32_t max_len, fws_frame_info *dev_frames, fws_msg_info *dev_msgs, void *dev_dst,
-                                 void *dev_ctl, fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
-                                 fws_msg_flow *dev_flows, uint32_t n_conns, void *stream) {
+// both roles of the flow decode: the checks, then the launch
+static int decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire, const fws_msg_read *dev_reads, uint32_t n,
+                                uint32_t max_len, fws_frame_info *dev_frames, fws_msg_info *dev_msgs, void *dev_dst,
+                                void *dev_ctl, fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
+                                fws_msg_flow *dev_flows, uint32_t n_conns, void *stream, bool client) {
     if (n == 0) return 0;
     if (!ctx || !dev_wire || !dev_reads || !dev_frames || !dev_msgs || !dev_dst || !dev_ctl || !dev_results ||
         !dev_msg_results || !dev_flows)
@@ -496,7 +497,24 @@ int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire, const f
     if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
     return fws_launch_msg_flow((const uint8_t *)dev_wire, dev_reads, n, max_len, dev_frames, dev_msgs,
                                (uint8_t *)dev_dst, (uint8_t *)dev_ctl, dev_results, dev_msg_results, dev_flows,
-                               n_conns, (hipStream_t)stream);
+                               n_conns, (hipStream_t)stream, client);
+}
+
+int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire, const fws_msg_read *dev_reads, uint32_t n,
+                                 uint32_t max_len, fws_frame_info *dev_frames, fws_msg_info *dev_msgs, void *dev_dst,
+                                 void *dev_ctl, fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
+                                 fws_msg_flow *dev_flows, uint32_t n_conns, void *stream) {
+    return decode_messages_flow(ctx, dev_wire, dev_reads, n, max_len, dev_frames, dev_msgs, dev_dst, dev_ctl,
+                                dev_results, dev_msg_results, dev_flows, n_conns, stream, false);
+}
+
+int fws_gpu_decode_messages_flow_client(fws_gpu_ctx *ctx, const void *dev_wire, const fws_msg_read *dev_reads,
+                                        uint32_t n, uint32_t max_len, fws_frame_info *dev_frames,
+                                        fws_msg_info *dev_msgs, void *dev_dst, void *dev_ctl,
+                                        fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
+                                        fws_msg_flow *dev_flows, uint32_t n_conns, void *stream) {
+    return decode_messages_flow(ctx, dev_wire, dev_reads, n, max_len, dev_frames, dev_msgs, dev_dst, dev_ctl,
+                                dev_results, dev_msg_results, dev_flows, n_conns, stream, true);
 }
 
 int fws_gpu_encode_messages_multi(fws_gpu_ctx *ctx, void *dev_out, const void *dev_src, const fws_tx_send *dev_sends,
@@ -513,13 +531,13 @@ int fws_gpu_encode_messages_multi(fws_gpu_ctx *ctx, void *dev_out, const void *d
                                dev_results, dev_conns, n_conns, (hipStream_t)stream);
 }
 
-int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
-                                 const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
-                                 const fws_msg_result *dev_msg_results, const fws_reply_region *dev_regions,
-                                 void *dev_out, fws_frame_info *dev_frames, fws_tx_result *dev_results,
-                                 fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
-                                 uint32_t flags, void *stream) {
-    if (n == 0) return 0;
+// both forms of the reply: the checks, then the launch (dev_keys non-null: client frames)
+static int reply_messages_multi(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                const fws_msg_result *dev_msg_results, const fws_reply_region *dev_regions,
+                                void *dev_out, fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                uint32_t flags, const uint32_t *dev_keys, void *stream) {
     // (dev_frames may be null: a read with frame_cap 0 writes no record)
     if (!ctx || !dev_reads || !dev_msgs || !dev_dst || !dev_ctl || !dev_msg_results || !dev_regions || !dev_out ||
         !dev_results || !dev_conns || !dev_states)
@@ -528,9 +546,67 @@ int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads
     if (max_len < 1u || max_len > FWS_MSG_MULTI_MAX_READ) return FWS_ERR_INVALID;
     if (flags & ~(FWS_REPLY_CONTROL | FWS_REPLY_ECHO)) return FWS_ERR_INVALID;
     if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
+    if (dev_keys)
+        return fws_launch_reply_client(dev_reads, n, max_len, dev_msgs, (const uint8_t *)dev_dst,
+                                       (const uint8_t *)dev_ctl, dev_msg_results, dev_regions, (uint8_t *)dev_out,
+                                       dev_frames, dev_results, dev_conns, dev_states, n_conns, flags, dev_keys,
+                                       (hipStream_t)stream);
     return fws_launch_reply(dev_reads, n, max_len, dev_msgs, (const uint8_t *)dev_dst, (const uint8_t *)dev_ctl,
                             dev_msg_results, dev_regions, (uint8_t *)dev_out, dev_frames, dev_results, dev_conns,
                             dev_states, n_conns, flags, (hipStream_t)stream);
+}
+
+int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                 const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                 const fws_msg_result *dev_msg_results, const fws_reply_region *dev_regions,
+                                 void *dev_out, fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                 fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                 uint32_t flags, void *stream) {
+    if (n == 0) return 0;
+    return reply_messages_multi(ctx, dev_reads, n, max_len, dev_msgs, dev_dst, dev_ctl, dev_msg_results, dev_regions,
+                                dev_out, dev_frames, dev_results, dev_conns, dev_states, n_conns, flags, nullptr,
+                                stream);
+}
+
+int fws_gpu_reply_messages_multi_client(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                        const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                        const fws_msg_result *dev_msg_results, const fws_reply_region *dev_regions,
+                                        void *dev_out, fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                        fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                        uint32_t flags, const uint32_t *dev_keys, void *stream) {
+    if (n == 0) return 0;
+    if (!dev_keys) return FWS_ERR_INVALID;
+    return reply_messages_multi(ctx, dev_reads, n, max_len, dev_msgs, dev_dst, dev_ctl, dev_msg_results, dev_regions,
+                                dev_out, dev_frames, dev_results, dev_conns, dev_states, n_conns, flags, dev_keys,
+                                stream);
+}
+
+static int reply_messages_strict(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                 const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                 const fws_msg_result *dev_msg_results, const void *dev_conn_states,
+                                 uint32_t conn_state_stride, uint64_t max_message_bytes,
+                                 const fws_reply_region *dev_regions, void *dev_out, fws_frame_info *dev_frames,
+                                 fws_tx_result *dev_results, fws_tx_conn *dev_conns, fws_reply_state *dev_states,
+                                 uint32_t n_conns, uint32_t flags, const uint32_t *dev_keys, void *stream) {
+    // (dev_frames may be null: a read with frame_cap 0 writes no record)
+    if (!ctx || !dev_reads || !dev_msgs || !dev_dst || !dev_ctl || !dev_msg_results || !dev_conn_states ||
+        !dev_regions || !dev_out || !dev_results || !dev_conns || !dev_states)
+        return FWS_ERR_INVALID;
+    if (conn_state_stride != sizeof(fws_msg_carry) && conn_state_stride != sizeof(fws_msg_flow)) return FWS_ERR_INVALID;
+    if (((uintptr_t)dev_out & 15u) != 0) return FWS_ERR_INVALID;
+    if (max_len < 1u || max_len > FWS_MSG_MULTI_MAX_READ) return FWS_ERR_INVALID;
+    if (flags & ~(FWS_REPLY_CONTROL | FWS_REPLY_ECHO)) return FWS_ERR_INVALID;
+    if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
+    if (dev_keys)
+        return fws_launch_reply_strict_client(dev_reads, n, max_len, dev_msgs, (const uint8_t *)dev_dst,
+                                              (const uint8_t *)dev_ctl, dev_msg_results,
+                                              (const uint8_t *)dev_conn_states, conn_state_stride, max_message_bytes,
+                                              dev_regions, (uint8_t *)dev_out, dev_frames, dev_results, dev_conns,
+                                              dev_states, n_conns, flags, dev_keys, (hipStream_t)stream);
+    return fws_launch_reply_strict(dev_reads, n, max_len, dev_msgs, (const uint8_t *)dev_dst, (const uint8_t *)dev_ctl,
+                                   dev_msg_results, (const uint8_t *)dev_conn_states, conn_state_stride,
+                                   max_message_bytes, dev_regions, (uint8_t *)dev_out, dev_frames, dev_results,
+                                   dev_conns, dev_states, n_conns, flags, (hipStream_t)stream);
 }
 
 int fws_gpu_reply_messages_strict(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
@@ -541,19 +617,24 @@ int fws_gpu_reply_messages_strict(fws_gpu_ctx *ctx, const fws_msg_read *dev_read
                                   fws_tx_result *dev_results, fws_tx_conn *dev_conns, fws_reply_state *dev_states,
                                   uint32_t n_conns, uint32_t flags, void *stream) {
     if (n == 0) return 0;
-    // (dev_frames may be null: a read with frame_cap 0 writes no record)
-    if (!ctx || !dev_reads || !dev_msgs || !dev_dst || !dev_ctl || !dev_msg_results || !dev_conn_states ||
-        !dev_regions || !dev_out || !dev_results || !dev_conns || !dev_states)
-        return FWS_ERR_INVALID;
-    if (conn_state_stride != sizeof(fws_msg_carry) && conn_state_stride != sizeof(fws_msg_flow)) return FWS_ERR_INVALID;
-    if (((uintptr_t)dev_out & 15u) != 0) return FWS_ERR_INVALID;
-    if (max_len < 1u || max_len > FWS_MSG_MULTI_MAX_READ) return FWS_ERR_INVALID;
-    if (flags & ~(FWS_REPLY_CONTROL | FWS_REPLY_ECHO)) return FWS_ERR_INVALID;
-    if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
-    return fws_launch_reply_strict(dev_reads, n, max_len, dev_msgs, (const uint8_t *)dev_dst, (const uint8_t *)dev_ctl,
-                                   dev_msg_results, (const uint8_t *)dev_conn_states, conn_state_stride,
-                                   max_message_bytes, dev_regions, (uint8_t *)dev_out, dev_frames, dev_results,
-                                   dev_conns, dev_states, n_conns, flags, (hipStream_t)stream);
+    return reply_messages_strict(ctx, dev_reads, n, max_len, dev_msgs, dev_dst, dev_ctl, dev_msg_results,
+                                 dev_conn_states, conn_state_stride, max_message_bytes, dev_regions, dev_out,
+                                 dev_frames, dev_results, dev_conns, dev_states, n_conns, flags, nullptr, stream);
+}
+
+int fws_gpu_reply_messages_strict_client(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n,
+                                         uint32_t max_len, const fws_msg_info *dev_msgs, const void *dev_dst,
+                                         const void *dev_ctl, const fws_msg_result *dev_msg_results,
+                                         const void *dev_conn_states, uint32_t conn_state_stride,
+                                         uint64_t max_message_bytes, const fws_reply_region *dev_regions,
+                                         void *dev_out, fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                         fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                         uint32_t flags, const uint32_t *dev_keys, void *stream) {
+    if (n == 0) return 0;
+    if (!dev_keys) return FWS_ERR_INVALID;
+    return reply_messages_strict(ctx, dev_reads, n, max_len, dev_msgs, dev_dst, dev_ctl, dev_msg_results,
+                                 dev_conn_states, conn_state_stride, max_message_bytes, dev_regions, dev_out,
+                                 dev_frames, dev_results, dev_conns, dev_states, n_conns, flags, dev_keys, stream);
 }
 
 }  // extern "C"

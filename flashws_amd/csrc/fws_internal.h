@@ -339,11 +339,12 @@ int fws_launch_msg_multi(const uint8_t *wire, const fws_msg_read *reads, uint32_
                          fws_frame_info *frames, fws_msg_info *msgs, uint8_t *dst, uint8_t *ctl,
                          fws_decode_result *res, fws_msg_result *mres, fws_msg_carry *carries, uint32_t n_conns,
                          hipStream_t s);
-// fws_gpu_decode_messages_flow (msg_flow_kernels.hip): the same with a data frame in progress in the state
+// fws_gpu_decode_messages_flow (msg_flow_kernels.hip): the same with a data frame in progress in the state;
+// client: the header parse's client role (fws_gpu_decode_messages_flow_client)
 int fws_launch_msg_flow(const uint8_t *wire, const fws_msg_read *reads, uint32_t n, uint32_t max_len,
                         fws_frame_info *frames, fws_msg_info *msgs, uint8_t *dst, uint8_t *ctl,
                         fws_decode_result *res, fws_msg_result *mres, fws_msg_flow *flows, uint32_t n_conns,
-                        hipStream_t s);
+                        hipStream_t s, bool client = false);
 // fws_gpu_encode_messages_multi (tx_multi_kernels.hip): n sends, one workgroup each; no workspace
 int fws_launch_tx_multi(uint8_t *out, const uint8_t *src, const fws_tx_send *sends, uint32_t n, uint32_t max_len,
                         fws_frame_info *frames, fws_tx_result *res, fws_tx_conn *conns, uint32_t n_conns,
@@ -354,6 +355,13 @@ int fws_launch_reply(const fws_msg_read *reads, uint32_t n, uint32_t max_len, co
                      const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
                      const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames, fws_tx_result *res,
                      fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns, uint32_t flags, hipStream_t s);
+// fws_gpu_reply_messages_multi_client (reply_client_kernels.hip): the same writing masked client frames; keys
+// (device) holds one word per read
+int fws_launch_reply_client(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
+                            const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
+                            const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames,
+                            fws_tx_result *res, fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns,
+                            uint32_t flags, const uint32_t *keys, hipStream_t s);
 
 // fws_gpu_reply_messages_strict (reply_strict_kernels.hip): the same with the first failing item of a read answered
 // by a CLOSE that carries the status code; conn_states is the decode call's state array (stride 64 or 96), read only.
@@ -363,6 +371,14 @@ int fws_launch_reply_strict(const fws_msg_read *reads, uint32_t n, uint32_t max_
                             const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames, fws_tx_result *res,
                             fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns, uint32_t flags,
                             hipStream_t s);
+// fws_gpu_reply_messages_strict_client (reply_strict_client_kernels.hip): the same writing masked client frames
+int fws_launch_reply_strict_client(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
+                                   const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
+                                   const uint8_t *conn_states, uint32_t conn_state_stride,
+                                   uint64_t max_message_bytes, const fws_reply_region *regions, uint8_t *out,
+                                   fws_frame_info *frames, fws_tx_result *res, fws_tx_conn *conns,
+                                   fws_reply_state *states, uint32_t n_conns, uint32_t flags, const uint32_t *keys,
+                                   hipStream_t s);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
                        hipStream_t s, const uint32_t *deny = nullptr);

@@ -30,6 +30,17 @@
 // 15 bytes back (the zero chunk in front when its payload starts below 15), and
 // the last window of an element that ends at N starts at or below N - 1 and ends
 // below N + 20 <= 16 * nch + 32.
+//
+// kServer false is the client role (fws_gpu_decode_messages_flow_client): the
+// header parse takes its client branch -- a MASK bit is FWS_ERR_MASKED, the
+// header is 2, 4 or 10 bytes, the key is 0 -- and nothing else differs. The
+// gather XORs with the zero key, so both roles run one copy of every phase and
+// frame_key stays 0. The padding argument above holds with room to spare: a
+// payload now starts at 2 or more, not 6, so a window still reaches at most 15
+// bytes back (into the zero chunk), and a header window at the last offset
+// reads the same 16 bytes behind it. What two-byte headers change is the count:
+// a read of N bytes holds up to N / 2 headers, which the walk's stop at header
+// kMfFrames + 1 bounds as before.
 #include "fws_device.h"
 #include "fws_internal.h"
 #include "msg_small_common.h"
@@ -69,7 +80,7 @@ struct MfHead {
     uint32_t old_tail, old_bad;
 };
 
-template <uint32_t kStage, uint32_t kThreads>
+template <uint32_t kStage, uint32_t kThreads, bool kServer>
 __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
     constexpr uint32_t kChunks = kStage / 16u;
     __shared__ u32x4 s_buf[kChunks + 3];            // a zero chunk in front, the read, two zero chunks
@@ -141,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_msg_flow(MfArgs a) {
             const uint32_t q = (uint32_t)pos;
             const uint32_t bl = sb[q + (lane & 15u)];        // (in bounds: s_buf has a chunk past N)
             const int rc = parse_hdr([&](int i) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)bl, i); },
-                                     N - q, true, h);
+                                     N - q, kServer, h);
             if (rc < 0) { r.status = rc; r.err_off = q; break; }
             if (rc == 0) break;                               // incomplete trailing header
             if (nf == kMfFrames) { capped = true; ++nf; break; }   // header kMfFrames + 1: the caller continues here
@@ -314,14 +325,19 @@ constexpr uint32_t kMfSmallStage = 16u << 10;
 int fws_launch_msg_flow(const uint8_t *wire, const fws_msg_read *reads, uint32_t n, uint32_t max_len,
                         fws_frame_info *frames, fws_msg_info *msgs, uint8_t *dst, uint8_t *ctl,
                         fws_decode_result *res, fws_msg_result *mres, fws_msg_flow *flows, uint32_t n_conns,
-                        hipStream_t s) {
+                        hipStream_t s, bool client) {
     static_assert(FWS_MSG_MULTI_MAX_READ == kSmallMax && FWS_MSG_MULTI_MAX_FRAMES == kSmallFrames, "the small-read limits");
     static_assert(sizeof(fws_msg_flow) == 96 && offsetof(fws_msg_flow, frame_unread) == 64, "the state's layout");
     if (!n) return 0;
     MfArgs a{wire, reads, frames, msgs, dst, ctl, res, mres, flows, n_conns, max_len};
-    if (max_len <= kMfSmallStage)
-        hipLaunchKernelGGL((k_msg_flow<kMfSmallStage, 256u>), dim3(n), dim3(256), 0, s, a);
+    if (client) {
+        if (max_len <= kMfSmallStage)
+            hipLaunchKernelGGL((k_msg_flow<kMfSmallStage, 256u, false>), dim3(n), dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_msg_flow<(uint32_t)kSmallMax, 1024u, false>), dim3(n), dim3(1024), 0, s, a);
+    } else if (max_len <= kMfSmallStage)
+        hipLaunchKernelGGL((k_msg_flow<kMfSmallStage, 256u, true>), dim3(n), dim3(256), 0, s, a);
     else
-        hipLaunchKernelGGL((k_msg_flow<(uint32_t)kSmallMax, 1024u>), dim3(n), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL((k_msg_flow<(uint32_t)kSmallMax, 1024u, true>), dim3(n), dim3(1024), 0, s, a);
     return fws_hip_status(hipGetLastError());
 }

@@ -6,6 +6,14 @@
 // offset's frame in it, the seam-chunk builder over it (tx_multi_common.h holds
 // the byte builders themselves), the byte phase and the frame records. The
 // classification of the items and the table fill stay with each kernel.
+//
+// kMasked: the client form (fws_gpu_reply_messages_*_client). Every frame has
+// the MASK bit and a key, FWS_TX_FRAG_KEY(key0, j) for frame j of the region
+// (key0: the read's word of dev_keys), so the key is a function of the frame
+// index the table search already gives and the table holds none. The payload
+// is XORed from phase 0: a 4-aligned dword at region offset av of a frame whose
+// payload starts at P takes the key rotated to (av - P) & 3. With kMasked false
+// key0 is unused and the code is what it was.
 #pragma once
 
 #include "fws_device.h"
@@ -28,8 +36,9 @@ __device__ __forceinline__ void rp_result(fws_tx_result *res, uint32_t r, int32_
 
 // Frame index and offset: the workgroup scan of a thread's (frames, bytes) over
 // its consecutive items. pc / pb: frames / bytes before the thread's first item;
-// nf / total: the read's (a frame is at most 128 KiB + 10 and there are fewer
-// than 260: no overflow). s_wc / s_wb: kWaves words each; passes one barrier.
+// nf / total: the read's (a frame is at most 128 KiB + 14 and there are fewer
+// than 260: under 2^26, no overflow). s_wc / s_wb: kWaves words each; passes one
+// barrier.
 struct RpScan {
     uint32_t pc, pb, nf, total;
 };
@@ -61,7 +70,8 @@ struct RpTable {
     uint32_t bh[kRpItems];         // b0 | header bytes << 8
 };
 
-__device__ __forceinline__ TmFrame rp_frame(const RpTable &t, uint32_t j) {
+template <bool kMasked>
+__device__ __forceinline__ TmFrame rp_frame(const RpTable &t, uint32_t j, uint32_t key0) {
     TmFrame f;
     f.O = t.off[j];
     f.plen = t.len[j];
@@ -70,7 +80,7 @@ __device__ __forceinline__ TmFrame rp_frame(const RpTable &t, uint32_t j) {
     f.P = f.O + f.hlen;
     f.E = f.P + f.plen;
     f.soff = 0u;
-    f.key = 0u;
+    f.key = kMasked ? FWS_TX_FRAG_KEY(key0, j) : 0u;
     return f;
 }
 
@@ -88,15 +98,18 @@ __device__ __forceinline__ uint32_t rp_frame_of(const RpTable &t, uint32_t nf, u
 // gives its header bytes and its payload bytes; bytes at or past the total stay
 // zero. A source block that holds no byte of the frame's payload is replaced by
 // one that does (its bytes are never selected), so every load is in bounds.
-__device__ u32x4 rp_seam_chunk(const RpTable &t, uint32_t nf, uint32_t a, uint32_t j) {
+// Masked: the window is XORed with the key at the window's payload phase before
+// it is selected.
+template <bool kMasked>
+__device__ u32x4 rp_seam_chunk(const RpTable &t, uint32_t nf, uint32_t a, uint32_t j, uint32_t key0) {
     u32x4 x{0u, 0u, 0u, 0u};
     for (; j < nf; ++j) {
-        const TmFrame f = rp_frame(t, j);
+        const TmFrame f = rp_frame<kMasked>(t, j, key0);
         if (f.O >= a + 16u) break;
         const uint32_t ho = tm_rel(f.O, a), hp = tm_rel(f.P, a), he = tm_rel(f.E, a);
-        if (hp > ho) {                                 // -16 < a - O < 16: the header is 10 bytes at most
+        if (hp > ho) {                                 // -16 < a - O < 16: the header is 14 bytes at most
             const int off = (int)a - (int)f.O;
-            if (off > -16 && off < 16) x = x | tm_and_sel(tm_bytes_at(tm_hdr_vec(f, false), off), ho, hp);
+            if (off > -16 && off < 16) x = x | tm_and_sel(tm_bytes_at(tm_hdr_vec(f, kMasked), off), ho, hp);
         }
         if (he > hp) {
             const uintptr_t s0 = (uintptr_t)t.src[j], s1 = s0 + f.plen;
@@ -105,7 +118,8 @@ __device__ u32x4 rp_seam_chunk(const RpTable &t, uint32_t nf, uint32_t a, uint32
             uintptr_t b0 = sa & ~uintptr_t(15), b1 = b0 + 16u;
             if (b0 + 16u <= s0 || b0 >= s1) b0 = safe;
             if (b1 + 16u <= s0 || b1 >= s1) b1 = safe;
-            const u32x4 w = tm_shr_bytes(gload16<false>(b0), gload16<false>(b1), (uint32_t)(sa & 15u));
+            u32x4 w = tm_shr_bytes(gload16<false>(b0), gload16<false>(b1), (uint32_t)(sa & 15u));
+            if constexpr (kMasked) w = w ^ rotr32(f.key, 8u * ((a - f.P) & 3u));
             x = x | tm_and_sel(w, hp, he);
         }
     }
@@ -117,16 +131,23 @@ __device__ u32x4 rp_seam_chunk(const RpTable &t, uint32_t nf, uint32_t a, uint32
 // frame by rp_frame_of; one inside a single payload is two aligned source loads
 // shifted by the source misalignment, any other (a seam: it meets a header or
 // the region's end) is built by rp_seam_chunk and stored up to the total.
-template <uint32_t kThreads>
+// Masked: what a full chunk's key needs is known with its addresses, before the
+// round's loads are issued -- the frame index, which the seam path keeps anyway,
+// and the payload phase (av - P) & 3, two bits a chunk packed into one register
+// -- so the eight loads of a thread stay in flight together and the key is
+// rotated and XORed into the shifted window on its way to the store. (The
+// masked form takes 66 registers against 60 either way; what is done about it
+// at 1024 threads is k_reply's launch bound)
+template <uint32_t kThreads, bool kMasked>
 __device__ __forceinline__ void rp_write_bytes(const RpTable &t, uint32_t nf, uint32_t total, uint8_t *R,
-                                               uint32_t lane, uint32_t wv) {
+                                               uint32_t lane, uint32_t wv, uint32_t key0) {
     const uint32_t nch = (total + 15u) >> 4;
     const uint32_t lane0 = wv * (64u * kTmU) + lane;
     for (uint32_t r0 = 0; r0 < nch; r0 += kThreads * kTmU) {   // (uniform trip count)
         const uint32_t c0 = r0 + lane0;
         uintptr_t sb[kTmU];
         uint32_t sh[kTmU], fj[kTmU];
-        uint32_t full = 0, seam = 0;
+        uint32_t full = 0, seam = 0, phases = 0;
 #pragma unroll
         for (uint32_t u = 0; u < kTmU; ++u) {
             const uint32_t c = c0 + u * 64u, av = c < nch ? c * 16u : 0u;
@@ -139,6 +160,7 @@ __device__ __forceinline__ void rp_write_bytes(const RpTable &t, uint32_t nf, ui
             const uintptr_t sa = (uintptr_t)t.src[j] + (uintptr_t)(av - P);
             sb[u] = sa & ~uintptr_t(15);
             sh[u] = (uint32_t)(sa & 15u);
+            if constexpr (kMasked) phases |= ((av - P) & 3u) << (2u * u);
         }
         u32x4 v0[kTmU], v1[kTmU];
 #pragma unroll
@@ -152,28 +174,32 @@ __device__ __forceinline__ void rp_write_bytes(const RpTable &t, uint32_t nf, ui
         }
 #pragma unroll
         for (uint32_t u = 0; u < kTmU; ++u)
-            if ((full >> u) & 1u)
-                gstore16<true>((uintptr_t)(R + (c0 + u * 64u) * 16u), tm_shr_bytes(v0[u], v1[u], sh[u]));
+            if ((full >> u) & 1u) {
+                u32x4 w = tm_shr_bytes(v0[u], v1[u], sh[u]);
+                if constexpr (kMasked) w = w ^ rotr32(FWS_TX_FRAG_KEY(key0, fj[u]), 8u * ((phases >> (2u * u)) & 3u));
+                gstore16<true>((uintptr_t)(R + (c0 + u * 64u) * 16u), w);
+            }
         if (seam) {
 #pragma unroll
             for (uint32_t u = 0; u < kTmU; ++u) {
                 if (!((seam >> u) & 1u)) continue;
                 const uint32_t av = (c0 + u * 64u) * 16u;
-                tm_store_chunk(R, av, total, rp_seam_chunk(t, nf, av, fj[u]));
+                tm_store_chunk(R, av, total, rp_seam_chunk<kMasked>(t, nf, av, fj[u], key0));
             }
         }
     }
 }
 
 // the records of the first nrec frames
-template <uint32_t kThreads>
-__device__ __forceinline__ void rp_put_records(const RpTable &t, uint32_t nrec, fws_frame_info *frames, uint32_t tid) {
+template <uint32_t kThreads, bool kMasked>
+__device__ __forceinline__ void rp_put_records(const RpTable &t, uint32_t nrec, fws_frame_info *frames, uint32_t tid,
+                                               uint32_t key0) {
     for (uint32_t j = tid; j < nrec; j += kThreads) {
-        const TmFrame f = rp_frame(t, j);
+        const TmFrame f = rp_frame<kMasked>(t, j, key0);
         fws_frame_info fi;
         fi.hdr_off = f.O;
         fi.payload_len = f.plen;
-        fi.key = 0u;
+        fi.key = f.key;
         fi.opcode = (uint8_t)(f.b0 & 15u);
         fi.fin = (uint8_t)(f.b0 >> 7);
         fi.hdr_len = (uint8_t)f.hlen;

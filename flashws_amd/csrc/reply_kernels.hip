@@ -27,10 +27,21 @@
 // (rp_write_bytes, reply_common.h, shared with k_reply_strict as the scan and
 // the frame records are). The region's last chunk is stored bytewise up to
 // out_len: no byte outside [out_off, out_off + out_len) is written.
+//
+// kMasked (fws_gpu_reply_messages_multi_client): the frames are client frames,
+// masked with FWS_TX_FRAG_KEY(keys[read], frame index); reply_common.h has the
+// byte phase. The walk, the refusals and both states are the same. The masked
+// instantiations are compiled in a translation unit of their own,
+// reply_client_kernels.hip, which includes this file with FWS_REPLY_CLIENT_TU
+// defined: instantiated next to the unmasked ones they changed those kernels'
+// code (other registers and, at 1024 threads, more instructions; apart, the
+// unmasked kernels are instruction for instruction what they were).
 #include "fws_device.h"
 #include "fws_internal.h"
 #include "reply_common.h"
 #include "tx_multi_common.h"
+
+#include <type_traits>
 
 namespace fwsk {
 
@@ -49,9 +60,24 @@ struct RpArgs {
     uint32_t n_conns;
     uint32_t flags;
 };
+// the masked form's arguments: RpArgs itself stays what the unmasked kernels take
+struct RpArgsMasked {
+    RpArgs r;
+    const uint32_t *keys;          // one word per read
+};
 
-template <uint32_t kThreads>
-__global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
+// (the second bound: the masked form takes 66 registers, two over what lets two workgroups of 1024 -- eight waves
+// a SIMD -- share a compute unit, so its 1024-thread form is held to 64 at the price of three spilled dwords:
+// 512 x 64 KiB 18.2 -> 16.6 us. The 256-thread form measured slower held to 64, and every other instantiation
+// gets the default value, its code unchanged)
+template <uint32_t kThreads, bool kMasked>
+__global__ __launch_bounds__(kThreads, kMasked && kThreads == 1024u ? 8u : kThreads / 256u)
+void k_reply(std::conditional_t<kMasked, RpArgsMasked, RpArgs> args) {
+    uint32_t key0 = 0u;
+    const RpArgs *ap;
+    if constexpr (kMasked) ap = &args.r, key0 = args.keys[blockIdx.x];
+    else ap = &args;
+    const RpArgs &a = *ap;
     constexpr uint32_t kIpt = (kRpItems + kThreads - 1u) / kThreads;   // items per thread, consecutive
     constexpr uint32_t kWaves = kThreads / 64u;
     __shared__ RpTable s_t;
@@ -162,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
 #pragma unroll
     for (uint32_t k = 0; k < kIpt; ++k) {
         if (tid * kIpt + k > fc) kind[k] = 0u;         // behind the CLOSE
-        if (kind[k]) cnt += 1u, byt += tm_hdr_len(len[k], false) + len[k];
+        if (kind[k]) cnt += 1u, byt += tm_hdr_len(len[k], kMasked) + len[k];
     }
     const uint32_t lane = tid & 63u, wv = tid >> 6;
     const RpScan sc = rp_scan<kWaves>(cnt, byt, s_wc, s_wb, lane, wv);
@@ -171,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
 #pragma unroll
     for (uint32_t k = 0; k < kIpt; ++k) {
         if (!kind[k]) continue;
-        const uint32_t i = tid * kIpt + k, hl = tm_hdr_len(len[k], false);
+        const uint32_t i = tid * kIpt + k, hl = tm_hdr_len(len[k], kMasked);
         // fws_tx_next: a data frame that continues an unfinished message is a continuation; FIN but on the open part
         const uint32_t b0 = kind[k] >= 3u ? ((kind[k] == 3u ? 0x80u : 0u) | ((i == fd && open) ? 0u : op[k])) : (0x80u | op[k]);
         s_t.src[pc] = src[k];
@@ -192,8 +218,8 @@ __global__ __launch_bounds__(kThreads) void k_reply(RpArgs a) {
     }
 
     // ---- the bytes, the frame records
-    rp_write_bytes<kThreads>(s_t, nf, total, a.out + g.out_off, lane, wv);
-    rp_put_records<kThreads>(s_t, nf < g.frame_cap ? nf : g.frame_cap, a.frames + g.frame_base, tid);
+    rp_write_bytes<kThreads, kMasked>(s_t, nf, total, a.out + g.out_off, lane, wv, key0);
+    rp_put_records<kThreads, kMasked>(s_t, nf < g.frame_cap ? nf : g.frame_cap, a.frames + g.frame_base, tid, key0);
 
     // ---- the result and both states, last
     if (tid == 0) {
@@ -218,6 +244,7 @@ using namespace fwsk;
 // threads, above 1024.
 constexpr uint32_t kRpSmallMax = 16u << 10;
 
+#ifndef FWS_REPLY_CLIENT_TU
 int fws_launch_reply(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
                      const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
                      const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames, fws_tx_result *res,
@@ -226,8 +253,23 @@ int fws_launch_reply(const fws_msg_read *reads, uint32_t n, uint32_t max_len, co
     if (!n) return 0;
     RpArgs a{out, dst, ctl, reads, msgs, mres, regions, frames, res, conns, states, n_conns, flags};
     if (max_len <= kRpSmallMax)
-        hipLaunchKernelGGL((k_reply<256u>), dim3(n), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_reply<256u, false>), dim3(n), dim3(256), 0, s, a);
     else
-        hipLaunchKernelGGL((k_reply<1024u>), dim3(n), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL((k_reply<1024u, false>), dim3(n), dim3(1024), 0, s, a);
     return fws_hip_status(hipGetLastError());
 }
+#else
+int fws_launch_reply_client(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
+                            const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
+                            const fws_reply_region *regions, uint8_t *out, fws_frame_info *frames,
+                            fws_tx_result *res, fws_tx_conn *conns, fws_reply_state *states, uint32_t n_conns,
+                            uint32_t flags, const uint32_t *keys, hipStream_t s) {
+    if (!n) return 0;
+    RpArgsMasked a{{out, dst, ctl, reads, msgs, mres, regions, frames, res, conns, states, n_conns, flags}, keys};
+    if (max_len <= kRpSmallMax)
+        hipLaunchKernelGGL((k_reply<256u, true>), dim3(n), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_reply<1024u, true>), dim3(n), dim3(1024), 0, s, a);
+    return fws_hip_status(hipGetLastError());
+}
+#endif

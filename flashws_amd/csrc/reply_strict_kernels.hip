@@ -20,10 +20,18 @@
 // items behind it give no frame, and the scan, the table and the byte phases
 // run as in k_reply (reply_common.h). The array is one aligned 16-byte block,
 // so the seam path's "block that holds a byte of the payload" is the array.
+//
+// kMasked (fws_gpu_reply_messages_strict_client): client frames as in k_reply;
+// the failing CLOSE is a frame like any other, counted in the key's frame index:
+// 8 bytes, its two code bytes masked. As there, the masked instantiations are
+// compiled apart: reply_strict_client_kernels.hip includes this file with
+// FWS_REPLY_CLIENT_TU defined.
 #include "fws_device.h"
 #include "fws_internal.h"
 #include "reply_common.h"
 #include "tx_multi_common.h"
+
+#include <type_traits>
 
 namespace fwsk {
 
@@ -49,6 +57,10 @@ struct RsArgs {
     uint32_t stride;
     uint32_t n_conns;
     uint32_t flags;
+};
+struct RsArgsMasked {              // (as RpArgsMasked: RsArgs itself stays what the unmasked kernels take)
+    RsArgs r;
+    const uint32_t *keys;          // one word per read
 };
 
 __device__ __forceinline__ uint32_t rs_code_src(uint32_t code) {   // offset in kRsCodes
@@ -77,8 +89,13 @@ __device__ __forceinline__ uint32_t rs_close_code(const uint8_t *p, uint32_t n, 
     return !rs_code_valid(code) ? 1002u : (bad ? 1007u : 0u);
 }
 
-template <uint32_t kThreads>
-__global__ __launch_bounds__(kThreads) void k_reply_strict(RsArgs a) {
+template <uint32_t kThreads, bool kMasked>
+__global__ __launch_bounds__(kThreads) void k_reply_strict(std::conditional_t<kMasked, RsArgsMasked, RsArgs> args) {
+    uint32_t key0 = 0u;
+    const RsArgs *ap;
+    if constexpr (kMasked) ap = &args.r, key0 = args.keys[blockIdx.x];
+    else ap = &args;
+    const RsArgs &a = *ap;
     constexpr uint32_t kIpt = (kRsItems + kThreads - 1u) / kThreads;   // items per thread, consecutive
     constexpr uint32_t kWaves = kThreads / 64u;
     __shared__ RpTable s_t;
@@ -237,7 +254,7 @@ __global__ __launch_bounds__(kThreads) void k_reply_strict(RsArgs a) {
         const uint32_t i = tid * kIpt + k;
         if (i > cut) kind[k] = 0u;                     // behind the CLOSE, echoed or failing
         if (failing && i == cut) kind[k] = 5u, len[k] = 2u;
-        if (kind[k]) cnt += 1u, byt += tm_hdr_len(len[k], false) + len[k];
+        if (kind[k]) cnt += 1u, byt += tm_hdr_len(len[k], kMasked) + len[k];
     }
     const RpScan sc = rp_scan<kWaves>(cnt, byt, s_wc, s_wb, lane, wv);
     const uint32_t nf = sc.nf, total = sc.total;
@@ -245,7 +262,7 @@ __global__ __launch_bounds__(kThreads) void k_reply_strict(RsArgs a) {
 #pragma unroll
     for (uint32_t k = 0; k < kIpt; ++k) {
         if (!kind[k]) continue;
-        const uint32_t i = tid * kIpt + k, hl = tm_hdr_len(len[k], false);
+        const uint32_t i = tid * kIpt + k, hl = tm_hdr_len(len[k], kMasked);
         const bool data = kind[k] == 3u || kind[k] == 4u;
         // fws_tx_next: a data frame that continues an unfinished message is a continuation; FIN but on the open part
         const uint32_t b0 = data ? ((kind[k] == 3u ? 0x80u : 0u) | ((i == fd && open) ? 0u : op[k]))
@@ -275,8 +292,8 @@ __global__ __launch_bounds__(kThreads) void k_reply_strict(RsArgs a) {
     }
 
     // ---- the bytes, the frame records
-    rp_write_bytes<kThreads>(s_t, nf, total, a.out + g.out_off, lane, wv);
-    rp_put_records<kThreads>(s_t, nf < g.frame_cap ? nf : g.frame_cap, a.frames + g.frame_base, tid);
+    rp_write_bytes<kThreads, kMasked>(s_t, nf, total, a.out + g.out_off, lane, wv, key0);
+    rp_put_records<kThreads, kMasked>(s_t, nf < g.frame_cap ? nf : g.frame_cap, a.frames + g.frame_base, tid, key0);
 
     // ---- the result and both states, last
     if (tid == 0) {
@@ -301,6 +318,7 @@ using namespace fwsk;
 // Two forms by the decode call's max_len, as k_reply: up to 16 KiB 256 threads, above 1024.
 constexpr uint32_t kRsSmallMax = 16u << 10;
 
+#ifndef FWS_REPLY_CLIENT_TU
 int fws_launch_reply_strict(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
                             const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
                             const uint8_t *conn_states, uint32_t conn_state_stride, uint64_t max_message_bytes,
@@ -314,8 +332,26 @@ int fws_launch_reply_strict(const fws_msg_read *reads, uint32_t n, uint32_t max_
     RsArgs a{out, dst, ctl, reads, msgs, mres, conn_states, regions, frames, res, conns, states, max_message_bytes,
              conn_state_stride, n_conns, flags};
     if (max_len <= kRsSmallMax)
-        hipLaunchKernelGGL((k_reply_strict<256u>), dim3(n), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_reply_strict<256u, false>), dim3(n), dim3(256), 0, s, a);
     else
-        hipLaunchKernelGGL((k_reply_strict<1024u>), dim3(n), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL((k_reply_strict<1024u, false>), dim3(n), dim3(1024), 0, s, a);
     return fws_hip_status(hipGetLastError());
 }
+#else
+int fws_launch_reply_strict_client(const fws_msg_read *reads, uint32_t n, uint32_t max_len, const fws_msg_info *msgs,
+                                   const uint8_t *dst, const uint8_t *ctl, const fws_msg_result *mres,
+                                   const uint8_t *conn_states, uint32_t conn_state_stride,
+                                   uint64_t max_message_bytes, const fws_reply_region *regions, uint8_t *out,
+                                   fws_frame_info *frames, fws_tx_result *res, fws_tx_conn *conns,
+                                   fws_reply_state *states, uint32_t n_conns, uint32_t flags, const uint32_t *keys,
+                                   hipStream_t s) {
+    if (!n) return 0;
+    RsArgsMasked a{{out, dst, ctl, reads, msgs, mres, conn_states, regions, frames, res, conns, states,
+                    max_message_bytes, conn_state_stride, n_conns, flags}, keys};
+    if (max_len <= kRsSmallMax)
+        hipLaunchKernelGGL((k_reply_strict<256u, true>), dim3(n), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_reply_strict<1024u, true>), dim3(n), dim3(1024), 0, s, a);
+    return fws_hip_status(hipGetLastError());
+}
+#endif

@@ -4,6 +4,7 @@ net/w_socket.h, error codes of ParseFrameHdr). Device memory, streams and
 events come from torch; all compute runs in libfws_gpu.so's HIP kernels.
 """
 import ctypes as C
+import random
 
 import numpy as np
 import torch
@@ -456,6 +457,19 @@ def decode_messages_flow(ctx, wire, reads, n, max_len, frames, msgs, dst, ctl, r
                                               _ptr(flows), n_conns, _stream_handle(stream))
 
 
+def decode_messages_flow_client(ctx, wire, reads, n, max_len, frames, msgs, dst, ctl, results, msg_results, flows,
+                                n_conns, stream=None):
+    """fws_gpu_decode_messages_flow_client: decode_messages_flow in the client
+    role. The reads hold server frames: no MASK bit (a masked frame is
+    FWS_ERR_MASKED), headers of 2, 4 or 10 bytes, payload copied as it is. The
+    arguments and the state tensor are decode_messages_flow's; one connection's
+    state belongs to one role. Returns the call's status; nothing is
+    synchronised."""
+    return lib().fws_gpu_decode_messages_flow_client(ctx.h, _ptr(wire), _ptr(reads), n, max_len, _ptr(frames),
+                                                     _ptr(msgs), _ptr(dst), _ptr(ctl), _ptr(results),
+                                                     _ptr(msg_results), _ptr(flows), n_conns, _stream_handle(stream))
+
+
 def read_msg_flow(flows, conn=0):
     sz = _lib.MSG_FLOW.itemsize
     return np.frombuffer(flows[conn * sz:(conn + 1) * sz].cpu().numpy().tobytes(), dtype=_lib.MSG_FLOW)[0]
@@ -475,14 +489,21 @@ class MessageFlow:
     connection inside the same feed; there is no other path. A connection
     whose status is a protocol or sequencing error keeps it in status[conn];
     feeding it again raises, the others go on. max_read bounds one
-    connection's feed."""
+    connection's feed. role="client" decodes what a client receives (server
+    frames, fws_gpu_decode_messages_flow_client); a frame is then as short as 2
+    bytes and the frame slices are sized for that."""
 
-    def __init__(self, ctx, n_conns, max_read, device="cuda:0"):
-        self.ctx, self.n_conns, self.max_read = ctx, n_conns, max_read
+    def __init__(self, ctx, n_conns, max_read, device="cuda:0", role="server"):
+        if role not in ("server", "client"):
+            raise ValueError(f"role must be 'server' or 'client', not {role!r}")
+        self.ctx, self.n_conns, self.max_read, self.role = ctx, n_conns, max_read, role
+        self._decode = decode_messages_flow_client if role == "client" else decode_messages_flow
+        self._decode_name = "fws_gpu_decode_messages_flow" + ("_client" if role == "client" else "")
         if max_read + _lib.FWS_MSG_FLOW_MAX_PENDING > _lib.FWS_MSG_MULTI_MAX_READ:
             raise ValueError("max_read exceeds FWS_MSG_MULTI_MAX_READ - 138")
         self.slot = (max_read + _lib.FWS_MSG_FLOW_MAX_PENDING + 15) & ~15
-        self.cap = min(self.slot // 6 + 1, _lib.FWS_MSG_MULTI_MAX_FRAMES)
+        # the shortest frame: a server's reads hold masked frames (6 bytes), a client's unmasked ones (2)
+        self.cap = min(self.slot // (2 if role == "client" else 6) + 1, _lib.FWS_MSG_MULTI_MAX_FRAMES)
         self.msg_cap = self.cap + 1                   # a lead that completes a message, then one per frame
         self.dev = torch.device(device)
         u8 = dict(dtype=torch.uint8, device=self.dev)
@@ -519,9 +540,9 @@ class MessageFlow:
             self._d[k][:n * sz[k]].copy_(self._h[k][:n * sz[k]], non_blocking=True)
         max_len = max(1, max(map(len, bufs.values())))
         d = self._d
-        check("fws_gpu_decode_messages_flow",
-              decode_messages_flow(self.ctx, d["wire"], d["reads"], n, max_len, d["frames"], d["msgs"], d["dst"],
-                                   d["ctl"], d["res"], d["mres"], self.flows, self.n_conns, stream=stream))
+        check(self._decode_name,
+              self._decode(self.ctx, d["wire"], d["reads"], n, max_len, d["frames"], d["msgs"], d["dst"],
+                           d["ctl"], d["res"], d["mres"], self.flows, self.n_conns, stream=stream))
         self.calls += 1
         if self._queued:
             self._queued(conns, max_len, stream)
@@ -536,7 +557,7 @@ class MessageFlow:
             r, buf = mres[i], bufs[c]
             status = int(r["status"])
             if status in (_lib.FWS_ERR_DECLINED, _lib.FWS_ERR_INVALID):
-                raise FwsError(f"fws_gpu_decode_messages_flow refused the read of connection {c}", status)
+                raise FwsError(f"{self._decode_name} refused the read of connection {c}", status)
             entries = np.frombuffer(self._h["msgs"].numpy()[i * sz["msgs"]:i * sz["msgs"] + int(r["n_msgs"]) *
                                                             MSG_INFO.itemsize].tobytes(), dtype=MSG_INFO)
             dst = self._h["dst"].numpy()[i * self.slot:(i + 1) * self.slot]
@@ -1117,6 +1138,39 @@ def reply_messages_strict(ctx, reads, n, max_len, msgs, dst, ctl, msg_results, c
                                                _ptr(conns), _ptr(states), n_conns, flags, _stream_handle(stream))
 
 
+def reply_messages_multi_client(ctx, reads, n, max_len, msgs, dst, ctl, msg_results, regions, out, frames, results,
+                                conns, states, n_conns, flags, keys, stream=None):
+    """fws_gpu_reply_messages_multi_client: reply_messages_multi writing client
+    frames -- the MASK bit, 4 key bytes, the payload XORed. keys is a device
+    tensor of n uint32 words, one per read; frame j of read r is masked with
+    _lib.FWS_TX_FRAG_KEY(keys[r], j). The other arguments are
+    reply_messages_multi's, the decode call's tensors those of
+    decode_messages_flow_client. Returns the call's status; nothing is
+    synchronised."""
+    return lib().fws_gpu_reply_messages_multi_client(ctx.h, _ptr(reads), n, max_len, _ptr(msgs), _ptr(dst), _ptr(ctl),
+                                                     _ptr(msg_results), _ptr(regions), _ptr(out),
+                                                     _ptr(frames) if frames is not None else None, _ptr(results),
+                                                     _ptr(conns), _ptr(states), n_conns, flags,
+                                                     _ptr(keys) if keys is not None else None,
+                                                     _stream_handle(stream))
+
+
+def reply_messages_strict_client(ctx, reads, n, max_len, msgs, dst, ctl, msg_results, conn_states, conn_state_stride,
+                                 max_message_bytes, regions, out, frames, results, conns, states, n_conns, flags,
+                                 keys, stream=None):
+    """fws_gpu_reply_messages_strict_client: reply_messages_strict writing client
+    frames, keys as in reply_messages_multi_client; the failing CLOSE is a masked
+    frame of 8 bytes and counts in the key's frame index. Returns the call's
+    status; nothing is synchronised."""
+    return lib().fws_gpu_reply_messages_strict_client(ctx.h, _ptr(reads), n, max_len, _ptr(msgs), _ptr(dst),
+                                                      _ptr(ctl), _ptr(msg_results), _ptr(conn_states),
+                                                      conn_state_stride, max_message_bytes, _ptr(regions), _ptr(out),
+                                                      _ptr(frames) if frames is not None else None, _ptr(results),
+                                                      _ptr(conns), _ptr(states), n_conns, flags,
+                                                      _ptr(keys) if keys is not None else None,
+                                                      _stream_handle(stream))
+
+
 def read_reply_state(states, conn=0):
     sz = _lib.REPLY_STATE.itemsize
     return np.frombuffer(states[conn * sz:(conn + 1) * sz].cpu().numpy().tobytes(), dtype=_lib.REPLY_STATE)[0]
@@ -1137,19 +1191,33 @@ class MessageResponder:
     or a message over max_message bytes (0: no limit) gets its valid prefix
     answered and then a CLOSE with the status code; failed = {conn: code} lists
     these connections (flow.status[conn] keeps a decode error as before, and
-    the host drops the connection)."""
+    the host drops the connection). Over a client-role flow
+    (MessageFlow(role="client")) the launches are the _client calls and the
+    replies are masked: every call uploads one key per read with the
+    descriptors, key_fn(conn) -> u32 (random.getrandbits(32) by default), and
+    last_keys = {conn: key} keeps the last call's, so frame j of that call's
+    reply on conn was masked with _lib.FWS_TX_FRAG_KEY(last_keys[conn], j).
+    Over a server-role flow key_fn must be None."""
 
-    def __init__(self, flow, flags, device="cuda:0", strict=False, max_message=0):
+    def __init__(self, flow, flags, device="cuda:0", strict=False, max_message=0, key_fn=None):
         self.flow, self.flags, self.strict, self.max_message = flow, flags, bool(strict), int(max_message)
+        self.client = getattr(flow, "role", "server") == "client"
+        if key_fn is not None and not self.client:
+            raise ValueError("key_fn is for a client-role flow: a server's replies are not masked")
+        self.key_fn = key_fn if key_fn is not None else (lambda conn: random.getrandbits(32))
+        self.last_keys = {}
         self.failed = {}
         self.dev = torch.device(device)
         n = flow.n_conns
         # a read's replies: its payload bytes and a header per entry and for the open part
-        # (strict: and the 4 bytes of the failing CLOSE)
-        self.out_slot = (flow.slot + 10 * (flow.msg_cap + 1) + (4 if self.strict else 0) + 15) & ~15
+        # (strict: and the 4 bytes of the failing CLOSE; a client: and 4 key bytes per frame)
+        hdr = 14 if self.client else 10
+        fail = (8 if self.client else 4) if self.strict else 0
+        self.out_slot = (flow.slot + hdr * (flow.msg_cap + 1) + fail + 15) & ~15
         u8 = dict(dtype=torch.uint8, device=self.dev)
         pin = dict(dtype=torch.uint8, pin_memory=True)
-        self._sizes = dict(out=self.out_slot, res=_lib.TX_RESULT.itemsize, regions=_lib.REPLY_REGION.itemsize)
+        self._sizes = dict(out=self.out_slot, res=_lib.TX_RESULT.itemsize, regions=_lib.REPLY_REGION.itemsize,
+                           **(dict(keys=4) if self.client else {}))
         self._d = {k: torch.zeros(n * sz, **u8) for k, sz in self._sizes.items()}
         self._h = {k: torch.zeros(n * sz, **pin) for k, sz in self._sizes.items()}
         self.conns = torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
@@ -1164,7 +1232,9 @@ class MessageResponder:
 
     def _queued(self, conns, max_len, stream):
         n, d, f, sz = len(conns), self._d, self.flow._d, self._sizes
-        if self.strict:
+        if self.client:
+            self._queue_client(conns, max_len, stream)
+        elif self.strict:
             check("fws_gpu_reply_messages_strict",
                   reply_messages_strict(self.flow.ctx, f["reads"], n, max_len, f["msgs"], f["dst"], f["ctl"], f["mres"],
                                         self.flow.flows, _lib.MSG_FLOW.itemsize, self.max_message, d["regions"],
@@ -1180,6 +1250,24 @@ class MessageResponder:
             self._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
         if self.strict:
             self._h_states.copy_(self.states, non_blocking=True)
+
+    def _queue_client(self, conns, max_len, stream):
+        """The client form of the launch: the keys go up with it, one per read."""
+        n, d, f = len(conns), self._d, self.flow._d
+        self.last_keys = {c: int(self.key_fn(c)) & 0xFFFFFFFF for c in conns}
+        self._h["keys"].numpy()[:4 * n] = np.array([self.last_keys[c] for c in conns], dtype="<u4").view(np.uint8)
+        d["keys"][:4 * n].copy_(self._h["keys"][:4 * n], non_blocking=True)
+        if self.strict:
+            check("fws_gpu_reply_messages_strict_client",
+                  reply_messages_strict_client(self.flow.ctx, f["reads"], n, max_len, f["msgs"], f["dst"], f["ctl"],
+                                               f["mres"], self.flow.flows, _lib.MSG_FLOW.itemsize, self.max_message,
+                                               d["regions"], d["out"], None, d["res"], self.conns, self.states,
+                                               self.flow.n_conns, self.flags, d["keys"], stream=stream))
+        else:
+            check("fws_gpu_reply_messages_multi_client",
+                  reply_messages_multi_client(self.flow.ctx, f["reads"], n, max_len, f["msgs"], f["dst"], f["ctl"],
+                                              f["mres"], d["regions"], d["out"], None, d["res"], self.conns,
+                                              self.states, self.flow.n_conns, self.flags, d["keys"], stream=stream))
 
     def _synced(self, conns):
         n = len(conns)

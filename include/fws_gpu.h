@@ -501,14 +501,57 @@ typedef struct fws_msg_flow {      /* device memory; all zero = a new connection
  *             always enough.
  * A read longer than FWS_MSG_MULTI_MAX_READ is cut anywhere into pieces whose
  * calls are queued on one stream; they chain through dev_flows without the
- * host. Out of scope: the same for fws_gpu_decode_messages(_carry), client-side
- * streams, the C++ adapter and the FLoop hook. */
+ * host. This is the server role: every frame must be masked. A client's
+ * connections use fws_gpu_decode_messages_flow_client below. Out of scope: the
+ * same for fws_gpu_decode_messages(_carry), the C++ adapter and the FLoop hook. */
 int fws_gpu_decode_messages_flow(fws_gpu_ctx *ctx, const void *dev_wire,
                                  const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
                                  fws_frame_info *dev_frames, fws_msg_info *dev_msgs,
                                  void *dev_dst, void *dev_ctl,
                                  fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
                                  fws_msg_flow *dev_flows, uint32_t n_conns, void *stream);
+
+/* ---- the same for a client's connections -------------------------------------
+ * OnRecvData is templated on the role (WSClientSocket / WSServerSocket); what a
+ * client receives are server frames: no MASK bit, no key, payload in the clear
+ * (w_socket.h:518-521). fws_gpu_decode_messages_flow_client is
+ * fws_gpu_decode_messages_flow in that role. The arguments, the argument checks
+ * before any device call, n == 0, the fws_msg_read descriptors, the fws_msg_flow
+ * state, the kernel form chosen by max_len, isolation, ordering, the header
+ * limit, the capacity rules and every field written are that call's. What
+ * differs, and nothing else:
+ *   headers   are parsed in the client role. A header with the MASK bit set is
+ *             FWS_ERR_MASKED at that header, reported exactly as the other parse
+ *             errors are: fws_decode_result.status / err_off / consumed, and
+ *             fws_msg_result.status by the status order, the frames before it
+ *             delivered. A header is 2, 4 or 10 bytes: fws_frame_info.hdr_len is
+ *             one of these and fws_frame_info.key is 0. FWS_ERR_NOT_MASKED never
+ *             occurs.
+ *   payload   data and control payload bytes are copied as they are (an unmask
+ *             with key 0). The UTF-8 check, the entries, the open part,
+ *             FWS_MSG_CONTINUED, the lead and frame_unread / frame_len /
+ *             frame_fin are unchanged; frame_key is always 0.
+ *   control frames stay whole as there; a caller's pending bytes are fewer than
+ *             10 + 125.
+ *   headers per read  a frame may be as short as 2 bytes, so a read of len bytes
+ *             holds up to len / 2 headers (the server role: len / 6). The walk
+ *             still stops at header FWS_MSG_MULTI_MAX_FRAMES + 1 and the caller
+ *             continues from resume_off; a frame_cap of
+ *             min(len / 2 + 1, FWS_MSG_MULTI_MAX_FRAMES) never limits a read.
+ *   state     a connection's fws_msg_flow belongs to one role: it is written by
+ *             this call only or by fws_gpu_decode_messages_flow only. Mixing the
+ *             two on one state is a contract violation (the server role's
+ *             frame_key would be dropped).
+ * fws_gpu_reply_messages_multi_client / _strict_client answer what this call
+ * delivered with masked frames. Out of scope: a client role for
+ * fws_gpu_decode_messages, _carry, _multi, fws_gpu_decode_stream and
+ * fws_rx_session; the C++ adapter and the FLoop hook. */
+int fws_gpu_decode_messages_flow_client(fws_gpu_ctx *ctx, const void *dev_wire,
+                                        const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                        fws_frame_info *dev_frames, fws_msg_info *dev_msgs,
+                                        void *dev_dst, void *dev_ctl,
+                                        fws_decode_result *dev_results, fws_msg_result *dev_msg_results,
+                                        fws_msg_flow *dev_flows, uint32_t n_conns, void *stream);
 
 /* ---- batched stream decode: many independent streams ----------------------
  * fws_gpu_decode_stream over a list of independent streams (the buffers of
@@ -886,9 +929,10 @@ typedef struct fws_reply_region {  /* device memory, one per read */
  * n == 0 returns 0 and looks at nothing. Otherwise ctx and every pointer but
  * dev_frames must be non-null, dev_out 16-B aligned, max_len between 1 and
  * FWS_MSG_MULTI_MAX_READ and flags within the two bits defined, or the call
- * returns FWS_ERR_INVALID before any device call. Out of scope: masked (client)
- * replies (the decode has no client role yet); cutting a part into several
- * frames; the C++ adapter and the FLoop hook. This call answers whatever the
+ * returns FWS_ERR_INVALID before any device call. A client's replies, which must
+ * be masked, are fws_gpu_reply_messages_multi_client's below. Out of scope:
+ * cutting a part into several frames; the C++ adapter and the FLoop hook. This
+ * call answers whatever the
  * decode delivered -- a TEXT entry with utf8_ok == 0 is echoed like any other, a
  * decode that ended in a protocol error gets the replies to its valid prefix;
  * fws_gpu_reply_messages_strict below fails such a connection instead. */
@@ -970,8 +1014,9 @@ int fws_gpu_reply_messages_multi(fws_gpu_ctx *ctx,
  * n == 0 returns 0 and looks at nothing. Otherwise the checks of
  * fws_gpu_reply_messages_multi apply, dev_conn_states must be non-null and
  * conn_state_stride 64 or 96, or the call returns FWS_ERR_INVALID before any
- * device call. Out of scope: a reason in the failing CLOSE; masked (client)
- * replies; cutting a part into several frames; a limit per connection; stopping
+ * device call. A client's (masked) replies are
+ * fws_gpu_reply_messages_strict_client's below. Out of scope: a reason in the
+ * failing CLOSE; cutting a part into several frames; a limit per connection; stopping
  * the decode of a failed connection (the host drops it when it sees fail_code);
  * the C++ adapter and the FLoop hook. */
 int fws_gpu_reply_messages_strict(fws_gpu_ctx *ctx,
@@ -984,6 +1029,58 @@ int fws_gpu_reply_messages_strict(fws_gpu_ctx *ctx,
                                   fws_frame_info *dev_frames, fws_tx_result *dev_results,
                                   fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
                                   uint32_t flags, void *stream);
+
+/* ---- the same two calls for a client: masked replies ----------------------------
+ * A client's frames carry the MASK bit and a key (SendFrame in the client role,
+ * w_socket.h:857-871). fws_gpu_reply_messages_multi_client and
+ * fws_gpu_reply_messages_strict_client are fws_gpu_reply_messages_multi and
+ * fws_gpu_reply_messages_strict with one argument added between flags and
+ * stream, and they answer what fws_gpu_decode_messages_flow_client delivered.
+ *   dev_keys  device memory, one word per read: dev_keys[r] is read r's key. The
+ *             call only reads it. NULL is FWS_ERR_INVALID before any device call
+ *             (n == 0 still returns 0 and looks at nothing).
+ * Everything in the two contracts above holds: the items and their order, the
+ * "no frames" cases, the refusals and their order, both states, the strict
+ * failure table, max_len, ordering, the absence of a workspace, no byte written
+ * outside [out_off, out_off + out_len). What differs:
+ *   bytes     every frame is a client frame: the MASK bit, 4 key bytes behind
+ *             the length, the payload XORed with the key from phase 0 -- what
+ *             fws_gpu_encode_frames writes for the same payload, opcode, FIN,
+ *             masked = 1 and key. A header is 2 + 4 + (0 | 2 | 8) bytes.
+ *   keys      frame j of read r uses FWS_TX_FRAG_KEY(dev_keys[r], j), as a masked
+ *             send of fws_gpu_encode_messages_multi does. j counts the frames
+ *             written to the region from 0, in order, the strict call's failing
+ *             CLOSE included. (The reference draws a fresh random key per frame,
+ *             w_socket.h:860; any key is as good, and the caller supplies the
+ *             randomness per read.)
+ *   records   fws_frame_info.key is the frame's key: the records are the ones
+ *             fws_gpu_decode_messages_flow (the server role) reports for the
+ *             same bytes.
+ *   lengths   out_len, the FWS_ERR_CAPACITY test and wire_bytes count the 4 key
+ *             bytes of every frame. The strict failing CLOSE is 8 bytes: header
+ *             2, key 4, the code's 2 bytes masked.
+ *   strict    conn_state_stride is 64 or 96 as before; after
+ *             fws_gpu_decode_messages_flow_client it is 96.
+ * Out of scope, as above: a reason in the failing CLOSE, cutting a part into
+ * several frames, the C++ adapter and the FLoop hook. */
+int fws_gpu_reply_messages_multi_client(fws_gpu_ctx *ctx,
+                                        const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                        const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                        const fws_msg_result *dev_msg_results,
+                                        const fws_reply_region *dev_regions, void *dev_out,
+                                        fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                        fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                        uint32_t flags, const uint32_t *dev_keys, void *stream);
+int fws_gpu_reply_messages_strict_client(fws_gpu_ctx *ctx,
+                                         const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                                         const fws_msg_info *dev_msgs, const void *dev_dst, const void *dev_ctl,
+                                         const fws_msg_result *dev_msg_results,
+                                         const void *dev_conn_states, uint32_t conn_state_stride,
+                                         uint64_t max_message_bytes,
+                                         const fws_reply_region *dev_regions, void *dev_out,
+                                         fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                                         fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
+                                         uint32_t flags, const uint32_t *dev_keys, void *stream);
 
 /* Host-memory send for one connection: WSocket::SendFrame (w_socket.h:832-944)
  * for its next n frames, in order. Frame i = payloads[i][0..lens[i]) of

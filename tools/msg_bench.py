@@ -96,7 +96,31 @@ library built from the parent commit in two contexts (the A/A spread), and the
 strict call -- and the parent's strict call in both contexts where it has one.
 Every form's output is compared byte for byte first. SO is the parent commit's
 library.
-       python tools/msg_bench.py --reply-strict --parent-lib SO [--rounds R] [--steps S] [--out FILE]"""
+       python tools/msg_bench.py --reply-strict --parent-lib SO [--rounds R] [--steps S] [--out FILE]
+
+--reply-client measures fws_gpu_reply_messages_multi_client / _strict_client
+ on --reply's grid (n in {64, 512, 4096} x 4 KiB, {64, 512} x
+64 KiB), one decoded single-frame BIN message per read, echoed. HIP events
+around back-to-back launches through raw pointers; within each round,
+alternating, all on the same decode output:
+  k_reply, k_reply_strict                 this tree's server (unmasked) calls
+  k_reply_parent_a/b, k_reply_strict_parent_a/b   the same calls of a library
+                                          built from the parent commit, in two
+                                          contexts: the A/A spread. This tree's
+                                          server instantiations pass when within
+                                          twice that spread of the parent.
+  k_reply_client, k_reply_strict_client   the masked calls, same parts
+  k_tx_multi_masked                       fws_gpu_encode_messages_multi on masked
+                                          one-frame sends of the same payloads
+Checked first, byte for byte: this tree's unmasked output against the
+parent's, and the masked reply's region against the masked encode's (same keys).
+--flow-client measures fws_gpu_decode_messages_flow_client on --flow (i)'s reads
+with the masks and keys taken out (the same payloads, 4 bytes less per frame)
+against fws_gpu_decode_messages_flow on the masked reads, this tree's and the
+parent library's in two contexts (k_msg_flow's no-regression check). The
+client's dst, ctl and entries are compared with the server's first.
+       python tools/msg_bench.py --reply-client --parent-lib SO [--rounds R] [--steps S] [--out FILE]
+       python tools/msg_bench.py --flow-client --parent-lib SO [--grid-n N,..] [--grid-kib K,..] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -1031,6 +1055,237 @@ def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
     return out
 
 
+def reply_client_bench(n, size, parent_lib, rounds, steps):
+    """--reply-client: see the module docstring. size: the message's payload bytes."""
+    dev = torch.device("cuda:0")
+    P = C.CDLL(parent_lib)
+    for name, res_t, args in _lib.SIGNATURES:
+        if hasattr(P, name):
+            getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
+    assert hasattr(P, "fws_gpu_reply_messages_strict"), "--parent-lib has no reply calls"
+    rng = np.random.default_rng(41 * n + size)
+    hdr = [header(2, 1, size, int(rng.integers(0, 1 << 32))) for _ in range(min(n, 64))]
+    rlen = len(hdr[0]) + size
+    slot = (rlen + 15) & ~15
+    need = size + (2 if size < 126 else 4 if size <= 65535 else 10)
+    oslot = (need + 4 + 15) & ~15                     # (one region size for every form: the masked frame fits)
+    host = np.zeros((n, slot), dtype=np.uint8)
+    body = rng.integers(0, 256, (min(n, 64), size), dtype=np.uint8)
+    for r in range(n):
+        host[r, :len(hdr[0])] = np.frombuffer(hdr[r % 64], dtype=np.uint8)
+        host[r, len(hdr[0]):rlen] = body[r % 64]
+    u8 = dict(dtype=torch.uint8, device=dev)
+    cap, ctl_cap = 2, 16
+    wire = torch.from_numpy(host.reshape(-1)).to(dev)
+    dst, ctl = torch.zeros(n * slot, **u8), torch.zeros(n * ctl_cap, **u8)
+    frames, msgs = torch.zeros(n * cap * 24, **u8), torch.zeros(n * cap * 32, **u8)
+    res, mres = torch.zeros(n * 40, **u8), torch.zeros(n * 64, **u8)
+    flows = torch.zeros(n * _lib.MSG_FLOW.itemsize, **u8)
+    desc = np.zeros(n, dtype=_lib.MSG_READ)
+    regions = np.zeros(n, dtype=_lib.REPLY_REGION)
+    sends = np.zeros(n, dtype=_lib.TX_SEND)
+    keys = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype("<u4")
+    for r in range(n):
+        desc[r] = (r * slot, r * slot, r * ctl_cap, rlen, r, slot, ctl_cap, r * cap, cap, r * cap, cap, 0)
+        regions[r] = (r * oslot, oslot, 0, 0, 0, 0)
+        for k, v in dict(src_off=r * slot, out_off=r * oslot, len=size, out_cap=oslot, conn=r, key=int(keys[r]),
+                         frame_type=2, last=1, masked=1).items():
+            sends[r][k] = v
+    reads = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    d_regions = torch.from_numpy(regions.view(np.uint8).copy()).to(dev)
+    d_sends = torch.from_numpy(sends.view(np.uint8).copy()).to(dev)
+    d_keys = torch.from_numpy(keys.view(np.uint8).copy()).to(dev)
+    ctx = gpu.Ctx(0)
+    s = torch.cuda.current_stream()
+    pctx = []
+    for _ in range(2):
+        h = C.c_void_p()
+        assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0
+        pctx.append(h)
+    max_len = rlen
+    assert gpu.decode_messages_flow(ctx, wire, reads, n, max_len, frames, msgs, dst, ctl, res, mres, flows, n) == 0
+    torch.cuda.synchronize()
+    echo = _lib.FWS_REPLY_CONTROL | _lib.FWS_REPLY_ECHO
+    states = torch.zeros(n * _lib.REPLY_STATE.itemsize, **u8)    # (no CLOSE in the reads: never written)
+    ptr = [t.data_ptr() for t in (reads, msgs, dst, ctl, mres, d_regions, flows)]
+    # the timed launches of every form write into one set of buffers; the check before them gives each its own
+    shared = [torch.zeros(n * oslot, **u8), torch.zeros(n * _lib.TX_RESULT.itemsize, **u8),
+              torch.zeros(n * _lib.TX_CONN.itemsize, **u8)]
+
+    def form(fn, h, strict, masked):
+        own = [torch.zeros_like(x) for x in shared]
+        extra = (ptr[6], _lib.MSG_FLOW.itemsize, 0) if strict else ()
+        kp = (d_keys.data_ptr(),) if masked else ()
+
+        def launch(bufs):
+            o, t, c = (x.data_ptr() for x in bufs)
+            assert fn(h, ptr[0], n, max_len, ptr[1], ptr[2], ptr[3], ptr[4], *extra, ptr[5], o, None, t, c,
+                      states.data_ptr(), n, echo, *kp, s.cuda_stream) == 0
+        return dict(f=lambda i: launch(own), timed=lambda i: launch(shared), out=own[0], res=own[1], conns=own[2])
+
+    def tx_form():
+        own = [torch.zeros_like(x) for x in shared]
+
+        def launch(bufs):
+            o, t, c = (x.data_ptr() for x in bufs)
+            assert L.fws_gpu_encode_messages_multi(ctx.h, o, ptr[2], d_sends.data_ptr(), n, size, None, t, c, n,
+                                                   s.cuda_stream) == 0
+        return dict(f=lambda i: launch(own), timed=lambda i: launch(shared), out=own[0], res=own[1], conns=own[2])
+
+    L = _lib.lib()
+    forms = {"k_reply": form(L.fws_gpu_reply_messages_multi, ctx.h, False, False),
+             "k_reply_parent_a": form(P.fws_gpu_reply_messages_multi, pctx[0], False, False),
+             "k_reply_parent_b": form(P.fws_gpu_reply_messages_multi, pctx[1], False, False),
+             "k_reply_strict": form(L.fws_gpu_reply_messages_strict, ctx.h, True, False),
+             "k_reply_strict_parent_a": form(P.fws_gpu_reply_messages_strict, pctx[0], True, False),
+             "k_reply_strict_parent_b": form(P.fws_gpu_reply_messages_strict, pctx[1], True, False),
+             "k_reply_client": form(L.fws_gpu_reply_messages_multi_client, ctx.h, False, True),
+             "k_reply_strict_client": form(L.fws_gpu_reply_messages_strict_client, ctx.h, True, True),
+             "k_tx_multi_masked": tx_form()}
+    for v in forms.values():                          # checked first: every form's output, byte for byte
+        v["f"](0)
+    torch.cuda.synchronize()
+    for a, others in (("k_reply", ("k_reply_parent_a", "k_reply_parent_b", "k_reply_strict", "k_reply_strict_parent_a",
+                                   "k_reply_strict_parent_b")),
+                      ("k_reply_client", ("k_reply_strict_client", "k_tx_multi_masked"))):
+        for k in others:
+            assert all(torch.equal(forms[a][x], forms[k][x]) for x in ("out", "res", "conns")), k
+    for k, want in (("k_reply", need), ("k_reply_client", need + 4)):
+        t = np.frombuffer(forms[k]["res"].cpu().numpy().tobytes(), dtype=_lib.TX_RESULT)
+        assert (t["status"] == 0).all() and (t["out_len"] == want).all() and (t["n_frames"] == 1).all(), k
+    out = {"measure": "reply_client", "n": n, "part_bytes": size, "form": "small" if rlen <= (16 << 10) else "full",
+           "reply_bytes": n * need, "reply_bytes_masked": n * (need + 4), "rounds": rounds, "steps": steps,
+           "device": torch.cuda.get_device_name(0), "parent_lib": os.path.basename(parent_lib)}
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(timed(forms[k]["timed"], steps))
+    for k in forms:
+        out[k + "_us"] = round(statistics.median(times[k]), 2)
+        out[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    for k in ("k_reply", "k_reply_strict"):           # the server instantiations against the parent's
+        pa, pb = out[k + "_parent_a_us"], out[k + "_parent_b_us"]
+        out[k + "_aa_spread_us"] = round(abs(pa - pb), 2)
+        out[k + "_minus_parent_us"] = round(out[k + "_us"] - min(pa, pb), 2)
+        out[k + "_within_twice_the_spread"] = bool(out[k + "_us"] - min(pa, pb) <= 2 * abs(pa - pb))
+    out["masked_over_unmasked"] = round(out["k_reply_client_us"] / out["k_reply_us"], 3)
+    out["strict_masked_over_unmasked"] = round(out["k_reply_strict_client_us"] / out["k_reply_strict_us"], 3)
+    out["masked_over_tx_multi_masked"] = round(out["k_reply_client_us"] / out["k_tx_multi_masked_us"], 3)
+    out["k_reply_gb_s"] = round(n * need / out["k_reply_us"] / 1e3, 2)
+    out["k_reply_client_gb_s"] = round(n * (need + 4) / out["k_reply_client_us"] / 1e3, 2)
+    out["k_tx_multi_masked_gb_s"] = round(n * (need + 4) / out["k_tx_multi_masked_us"] / 1e3, 2)
+    for h in pctx:
+        P.fws_gpu_ctx_destroy(h)
+    ctx.close()
+    return out
+
+
+def client_read(wire):
+    """A read of whole masked frames as a server writes it: the same payloads, no MASK bit, no key."""
+    out, pos = bytearray(), 0
+    while pos < len(wire):
+        b1 = wire[pos + 1]
+        assert b1 & 0x80
+        n, h = b1 & 127, 2
+        if n == 126:
+            n, h = struct.unpack(">H", wire[pos + 2:pos + 4])[0], 4
+        elif n == 127:
+            n, h = struct.unpack(">Q", wire[pos + 2:pos + 10])[0], 10
+        key = np.frombuffer(wire[pos + h:pos + h + 4], dtype=np.uint8)
+        body = np.frombuffer(wire[pos + h + 4:pos + h + 4 + n], dtype=np.uint8) ^ np.resize(key, n)
+        out += bytes([wire[pos], b1 & 0x7F]) + wire[pos + 2:pos + h] + body.tobytes()
+        pos += h + 4 + n
+    assert pos == len(wire)
+    return bytes(out)
+
+
+def flow_client_bench(n, size, parent_lib, rounds, steps):
+    """--flow-client: see the module docstring."""
+    dev = torch.device("cuda:0")
+    P = C.CDLL(parent_lib)
+    for name, res_t, args in _lib.SIGNATURES:
+        if hasattr(P, name):
+            getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
+    assert hasattr(P, "fws_gpu_decode_messages_flow"), "--parent-lib has no flow call"
+    rng = np.random.default_rng(1000 * n + size)
+    distinct = [multi_read(rng, size) for _ in range(min(n, 64))]
+    cap = max(f for _, f in distinct) + 4
+    ctl_cap = 8 * (cap // 64 + 2)
+    unmasked = [client_read(w) for w, _ in distinct]
+    host = np.stack([np.frombuffer(w, dtype=np.uint8) for w, _ in distinct])
+    chost = np.zeros_like(host)
+    for i, w in enumerate(unmasked):
+        chost[i, :len(w)] = np.frombuffer(w, dtype=np.uint8)
+    pick = np.arange(n) % len(distinct)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    wire, cwire = torch.from_numpy(host[pick].reshape(-1)).to(dev), torch.from_numpy(chost[pick].reshape(-1)).to(dev)
+    dst, ctl = torch.zeros(n * size, **u8), torch.zeros(n * ctl_cap, **u8)
+    frames, msgs = torch.zeros(n * cap * 24, **u8), torch.zeros(n * cap * 32, **u8)
+    res, mres = torch.zeros(n * 40, **u8), torch.zeros(n * 64, **u8)
+    flows = torch.zeros(n * _lib.MSG_FLOW.itemsize, **u8)
+    desc, cdesc = np.zeros(n, dtype=_lib.MSG_READ), np.zeros(n, dtype=_lib.MSG_READ)
+    for r in range(n):
+        desc[r] = (r * size, r * size, r * ctl_cap, size, r, size, ctl_cap, r * cap, cap, r * cap, cap, 0)
+        cdesc[r] = desc[r]
+        cdesc[r]["len"] = len(unmasked[pick[r]])
+    reads = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+    creads = torch.from_numpy(cdesc.view(np.uint8).copy()).to(dev)
+    ctx = gpu.Ctx(0)
+    s = torch.cuda.current_stream()
+    pctx = []
+    for _ in range(2):
+        h = C.c_void_p()
+        assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0
+        pctx.append(h)
+
+    def form(h, fn, w, rd):
+        def f(i):
+            assert fn(h, w.data_ptr(), rd.data_ptr(), n, size, frames.data_ptr(), msgs.data_ptr(), dst.data_ptr(),
+                      ctl.data_ptr(), res.data_ptr(), mres.data_ptr(), flows.data_ptr(), n, s.cuda_stream) == 0
+        return f
+
+    L = _lib.lib()
+    forms = {"flow_parent_a": form(pctx[0], P.fws_gpu_decode_messages_flow, wire, reads),
+             "flow_parent_b": form(pctx[1], P.fws_gpu_decode_messages_flow, wire, reads),
+             "flow": form(ctx.h, L.fws_gpu_decode_messages_flow, wire, reads),
+             "flow_client": form(ctx.h, L.fws_gpu_decode_messages_flow_client, cwire, creads)}
+    want = None
+    for k, f in forms.items():                        # checked first
+        for t in (dst, ctl, frames, msgs, res, mres, flows):
+            t.zero_()
+        f(0)
+        torch.cuda.synchronize()
+        m = np.frombuffer(mres.cpu().numpy().tobytes(), dtype=_lib.MSG_RESULT).copy()
+        assert (m["status"] == 0).all() and (m["open_opcode"] == 0).all(), k
+        assert (m["resume_off"] == (cdesc["len"] if k == "flow_client" else size)).all(), k
+        m["resume_off"] = 0
+        # the server forms: every byte; the client: the bytes, the control payloads, the entries and the results
+        got = [t.clone() for t in (dst, ctl, msgs)] + [m.tobytes()]
+        got += [] if k == "flow_client" else [t.clone() for t in (frames, res, flows)]
+        want = want or got
+        for a, b in zip(got, want):
+            assert torch.equal(a, b) if isinstance(a, torch.Tensor) else a == b, k
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(timed(forms[k], steps))
+    out = {"measure": "flow_client", "n": n, "read_bytes": size, "form": "small" if size <= (16 << 10) else "full",
+           "wire_bytes": n * size, "client_wire_bytes": int(cdesc["len"].astype(np.int64).sum()), "rounds": rounds,
+           "steps": steps, "device": torch.cuda.get_device_name(0), "parent_lib": os.path.basename(parent_lib)}
+    for k in forms:
+        out[k + "_us"] = round(statistics.median(times[k]), 2)
+        out[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    base = min(out["flow_parent_a_us"], out["flow_parent_b_us"])
+    out["flow_aa_spread_us"] = round(abs(out["flow_parent_a_us"] - out["flow_parent_b_us"]), 2)
+    out["flow_minus_parent_us"] = round(out["flow_us"] - base, 2)
+    out["flow_within_twice_the_spread"] = bool(out["flow_us"] - base <= 2 * out["flow_aa_spread_us"])
+    out["client_over_server"] = round(out["flow_client_us"] / out["flow_us"], 3)
+    for h in pctx:
+        P.fws_gpu_ctx_destroy(h)
+    ctx.close()
+    return out
+
+
 def c3_stream(target):
     wire, descs, _ = gpu.config_c3(target=target)
     regions = np.zeros(len(descs), dtype=_lib.FRAME_DESC)
@@ -1140,9 +1395,30 @@ def main():
     ap.add_argument("--reply", action="store_true", help="measure fws_gpu_reply_messages_multi (see above)")
     ap.add_argument("--reply-strict", action="store_true",
                     help="measure fws_gpu_reply_messages_strict against the plain call and the parent's (see above)")
+    ap.add_argument("--reply-client", action="store_true",
+                    help="measure the masked (client) reply calls and the server calls against the parent's (see above)")
+    ap.add_argument("--flow-client", action="store_true",
+                    help="measure fws_gpu_decode_messages_flow_client and the server call against the parent's")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.reply_client or a.flow_client:
+        assert a.parent_lib, "--reply-client / --flow-client need --parent-lib"
+        lib = os.path.abspath(a.parent_lib)
+        if a.reply_client:
+            for n, kib in ((64, 4), (512, 4), (4096, 4), (64, 64), (512, 64)):
+                lines.append(json.dumps(reply_client_bench(n, kib << 10, lib, a.rounds, a.steps)))
+                print(lines[-1], flush=True)
+        else:
+            grid_n = "1,64,512" if a.grid_n == ap.get_default("grid_n") else a.grid_n
+            for kib in map(int, a.grid_kib.split(",")):
+                for n in map(int, grid_n.split(",")):
+                    lines.append(json.dumps(flow_client_bench(n, kib << 10, lib, a.rounds, a.steps)))
+                    print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.reply_strict:
         assert a.parent_lib, "--reply-strict needs --parent-lib"
         lib = os.path.abspath(a.parent_lib)
