@@ -1,7 +1,8 @@
 """GPU: the one-launch forms of the output-space batches (no plan launch):
-k_gather_one (fws_gpu_unmask_gather for <= 2048 regions: every workgroup keeps
-the whole dst prefix in LDS) against the plan + k_gather_fast path and the
-oracle (reassembly is pinned to the concatenation of the on_read
+k_gather_one / k_gather_one_w8 (fws_gpu_unmask_gather for <= 2048 regions when
+fws_internal_set_gather_one selects them: every workgroup keeps the whole dst
+prefix in LDS) against the plan + k_gather_fast path, the default since r06,
+and the oracle (reassembly is pinned to the concatenation of the on_read
 parts, tests/new-ws-echo/test_ws_server.cpp:205-206; the key at each region's
 phase is RotateR(key, 8 * phase), w_socket.h:758)."""
 import numpy as np
@@ -16,10 +17,12 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(params=["one", "plan", "plan_r05", "one_dpp", "one_w8", "one_w8_dpp"])
 def gather_mode(request):
-    """k_gather_one, plan + k_gather_fast (r06 kFlat: one load per chunk and
-    the neighbour lane's block by DPP; plan_r05: two loads per chunk),
-    k_gather_one with one load per chunk + DPP, and k_gather_one_w8 (8 waves
-    per SIMD, seam chunks after the full ones) (fws_internal_set_gather_dpp)."""
+    """k_gather_one, plan + k_gather_fast (the default since r06, kFlat: one
+    load per chunk and the neighbour lane's block by DPP; plan_r05: two loads
+    per chunk), k_gather_one with one load per chunk + DPP, and k_gather_one_w8
+    (8 waves per SIMD, seam chunks after the full ones)
+    (fws_internal_set_gather_dpp). Deterministic seam layouts through all of
+    these: test_gpu_gather_seams.py."""
     L = _lib.lib()
     old = L.fws_internal_set_gather_one(0 if request.param.startswith("plan") else 1)
     old_flat = L.fws_internal_set_gather_flat(0 if request.param == "plan_r05" else 1)
