@@ -109,6 +109,21 @@ FWS_PROTOCOL_ERRORS = (FWS_ERR_RSV, FWS_ERR_NOT_MASKED, FWS_ERR_MASKED, FWS_ERR_
                        FWS_ERR_SEQUENCE)
 
 
+# fws_gpu_join_messages: where a message lies, the connection's join state, an entry's record and a read's result
+FWS_JOIN_IN_DST = 0     # whole in this read: dev_dst, not copied
+FWS_JOIN_IN_STORE = 1   # joined in the connection's slot of dev_store
+FWS_JOIN_IN_CTL = 2     # a control frame: dev_ctl
+FWS_JOIN_NOWHERE = 3    # dropped: longer than half a slot
+FWS_JOIN_DROPPED = 1    # fws_join_info.flags
+JOIN_STATE = np.dtype([("open_opcode", "<u4"), ("half", "<u4"), ("dropped", "<u4"), ("reserved0", "<u4"),
+                       ("open_bytes", "<u8"), ("fill", "<u8")])
+JOIN_INFO = np.dtype([("off", "<u8"), ("len", "<u8"), ("opcode", "u1"), ("utf8_ok", "u1"), ("where", "u1"),
+                      ("flags", "u1"), ("reserved0", "<u4"), ("reserved", "<u8")])
+JOIN_RESULT = np.dtype([("status", "<i4"), ("n_joined", "<u4"), ("copied", "<u8"), ("open_opcode", "<u4"),
+                        ("dropped", "<u4"), ("reserved", "<u8")])
+assert JOIN_STATE.itemsize == 32 and JOIN_INFO.itemsize == 32 and JOIN_RESULT.itemsize == 32
+
+
 def close_code_valid(code):
     """Whether a status code may appear in a CLOSE frame: the registry as of RFC 6455 plus 1012-1014."""
     return 1000 <= code <= 1003 or 1007 <= code <= 1014 or 3000 <= code <= 4999
@@ -192,6 +207,7 @@ SIGNATURES = [
                                                  _P, _P]),
     ("fws_gpu_reply_messages_strict_client", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P,
                                                   _P, _P, _U32, _U32, _P, _P]),
+    ("fws_gpu_join_messages", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _U64, _P, _P, _P, _U32, _P]),
     ("fws_tx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_tx_session_destroy", None, [_P]),
     ("fws_tx_session_send", _I, [_P, _P, _P, _P, _P, _P, _U32, _P, _U64, _PU64]),

@@ -637,6 +637,23 @@ int fws_gpu_reply_messages_strict_client(fws_gpu_ctx *ctx, const fws_msg_read *d
                                  dev_frames, dev_results, dev_conns, dev_states, n_conns, flags, dev_keys, stream);
 }
 
+int fws_gpu_join_messages(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                          const fws_msg_info *dev_msgs, const void *dev_dst, const fws_msg_result *dev_msg_results,
+                          void *dev_store, uint64_t store_stride, fws_join_info *dev_joined,
+                          fws_join_result *dev_results, fws_join_state *dev_states, uint32_t n_conns, void *stream) {
+    if (n == 0) return 0;
+    if (!ctx || !dev_reads || !dev_msgs || !dev_dst || !dev_msg_results || !dev_store || !dev_joined || !dev_results ||
+        !dev_states)
+        return FWS_ERR_INVALID;
+    if ((((uintptr_t)dev_dst | (uintptr_t)dev_store) & 15u) != 0) return FWS_ERR_INVALID;
+    if (max_len < 1u || max_len > FWS_MSG_MULTI_MAX_READ) return FWS_ERR_INVALID;
+    if (store_stride < 32u || (store_stride & 31u) != 0) return FWS_ERR_INVALID;
+    if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
+    return fws_launch_join(dev_reads, n, max_len, dev_msgs, (const uint8_t *)dev_dst, dev_msg_results,
+                           (uint8_t *)dev_store, store_stride, dev_joined, dev_results, dev_states, n_conns,
+                           (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 int fws_decode_prepare(fws_gpu_ctx *ctx, uint64_t len, uint32_t cap, bool utf8) {

@@ -1292,3 +1292,164 @@ class MessageResponder:
         finally:
             self.flow._queued = self.flow._synced = None
         return units, self._replies
+
+
+def join_messages(ctx, reads, n, max_len, msgs, dst, msg_results, store, store_stride, joined, results, states,
+                  n_conns, stream=None):
+    """fws_gpu_join_messages: the messages that span reads put together on the
+    device. reads, msgs, dst and msg_results are the tensors the decode call
+    (decode_messages_flow, _flow_client or decode_messages_multi) was given,
+    max_len its value; store holds n_conns slots of store_stride bytes (two
+    halves each), joined one fws_join_info (_lib.JOIN_INFO) per decode entry at
+    the entry's index, results n fws_join_result (_lib.JOIN_RESULT), states
+    n_conns fws_join_state (_lib.JOIN_STATE, zeros for new connections). Returns
+    the call's status; nothing is synchronised."""
+    return lib().fws_gpu_join_messages(ctx.h, _ptr(reads), n, max_len, _ptr(msgs), _ptr(dst), _ptr(msg_results),
+                                       _ptr(store), store_stride, _ptr(joined), _ptr(results), _ptr(states), n_conns,
+                                       _stream_handle(stream))
+
+
+def read_join_state(states, conn=0):
+    sz = _lib.JOIN_STATE.itemsize
+    return np.frombuffer(states[conn * sz:(conn + 1) * sz].cpu().numpy().tobytes(), dtype=_lib.JOIN_STATE)[0]
+
+
+class MessageJoiner:
+    """A MessageFlow whose messages are joined on the device: feed({conn:
+    bytes}) returns what flow.feed returns, but every data message's bytes are
+    read from where its fws_join_info record points -- the read's region of dst,
+    or, for a message that arrived over several reads, the connection's slot of
+    self.store (2 * align16(max_message) bytes, two halves), where a consumer on
+    the device finds it whole until the connection's next call. The join launch
+    is queued right behind each decode launch, the retries on the header limit
+    included; the join states (self.states) stay on the device, the host keeps
+    no parts (flow._parts is not used) and copies back from the store only the
+    messages delivered there. A message of more than align16(max_message) bytes
+    is dropped and returned as (opcode, None, utf8_ok).
+    A MessageJoiner stands in for its flow: MessageResponder(joiner, flags, ...)
+    answers on the device what the joiner decodes. The responder's hooks go on
+    the joiner, which calls them -- and any the flow itself carries -- around
+    its own launch; they are chained, not replaced."""
+
+    def __init__(self, flow, max_message, device="cuda:0"):
+        self.flow, self.max_message = flow, int(max_message)
+        self.half = max(16, (self.max_message + 15) & ~15)
+        self.stride = 2 * self.half
+        self.dev = torch.device(device)
+        n = flow.n_conns
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        pin = dict(dtype=torch.uint8, pin_memory=True)
+        self._jsizes = dict(joined=flow.msg_cap * _lib.JOIN_INFO.itemsize, jres=_lib.JOIN_RESULT.itemsize)
+        self._jd = {k: torch.zeros(n * sz, **u8) for k, sz in self._jsizes.items()}
+        self._jh = {k: torch.zeros(n * sz, **pin) for k, sz in self._jsizes.items()}
+        self.store = torch.zeros(n * self.stride, **u8)
+        self._h_store = torch.zeros(n * self.half, **pin)
+        self.states = torch.zeros(n * _lib.JOIN_STATE.itemsize, **u8)
+        self.calls = 0                                # fws_gpu_join_messages calls made
+        self.store_copies = 0                         # messages copied back from the store
+        self._queued = self._synced = None            # a MessageResponder's hooks, as on a MessageFlow
+
+    def __getattr__(self, name):                      # what a MessageResponder asks of its flow
+        if name == "flow":
+            raise AttributeError(name)
+        return getattr(self.flow, name)
+
+    def _call(self, bufs):
+        """MessageFlow._call with the join launch behind the decode launch: the units per connection."""
+        f = self.flow
+        conns, n = list(bufs), len(bufs)
+        sz, hw = f._sizes, f._h["wire"].numpy()
+        desc = np.zeros(n, dtype=MSG_READ)
+        for i, c in enumerate(conns):
+            buf = bufs[c]
+            hw[i * f.slot:i * f.slot + len(buf)] = np.frombuffer(buf, dtype=np.uint8)
+            desc[i] = (i * f.slot, i * f.slot, i * f.slot, len(buf), c, f.slot, f.slot, i * f.cap, f.cap,
+                       i * f.msg_cap, f.msg_cap, 0)
+            f.uploaded[c] += len(buf)
+        f._h["reads"].numpy()[:n * sz["reads"]] = desc.view(np.uint8)
+        stream = torch.cuda.current_stream(f.dev)
+        for k in ("wire", "reads"):
+            f._d[k][:n * sz[k]].copy_(f._h[k][:n * sz[k]], non_blocking=True)
+        max_len = max(1, max(map(len, bufs.values())))
+        d = f._d
+        check(f._decode_name,
+              f._decode(f.ctx, d["wire"], d["reads"], n, max_len, d["frames"], d["msgs"], d["dst"], d["ctl"],
+                        d["res"], d["mres"], f.flows, f.n_conns, stream=stream))
+        f.calls += 1
+        check("fws_gpu_join_messages",
+              join_messages(f.ctx, d["reads"], n, max_len, d["msgs"], d["dst"], d["mres"], self.store, self.stride,
+                            self._jd["joined"], self._jd["jres"], self.states, f.n_conns, stream=stream))
+        self.calls += 1
+        for hook in (f._queued, self._queued):
+            if hook:
+                hook(conns, max_len, stream)
+        for k in ("mres", "dst", "ctl"):
+            f._h[k][:n * sz[k]].copy_(d[k][:n * sz[k]], non_blocking=True)
+        for k, s in self._jsizes.items():
+            self._jh[k][:n * s].copy_(self._jd[k][:n * s], non_blocking=True)
+        stream.synchronize()
+        for hook in (f._synced, self._synced):
+            if hook:
+                hook(conns)
+        mres = np.frombuffer(f._h["mres"].numpy()[:n * sz["mres"]].tobytes(), dtype=MSG_RESULT)
+        jres = np.frombuffer(self._jh["jres"].numpy()[:n * self._jsizes["jres"]].tobytes(), dtype=_lib.JOIN_RESULT)
+        recs, stored = [], []
+        for i, c in enumerate(conns):
+            status = int(mres[i]["status"])
+            if status in (_lib.FWS_ERR_DECLINED, _lib.FWS_ERR_INVALID):
+                raise FwsError(f"{f._decode_name} refused the read of connection {c}", status)
+            if int(jres[i]["status"]):
+                raise FwsError(f"fws_gpu_join_messages refused the read of connection {c}", int(jres[i]["status"]))
+            o = i * self._jsizes["joined"]
+            r = np.frombuffer(self._jh["joined"].numpy()[o:o + int(jres[i]["n_joined"]) *
+                                                        _lib.JOIN_INFO.itemsize].tobytes(), dtype=_lib.JOIN_INFO)
+            recs.append(r)
+            stored += [(int(e["off"]), int(e["len"])) for e in r if e["where"] == _lib.FWS_JOIN_IN_STORE]
+        at, back = 0, {}
+        for off, ln in stored:                        # (a read delivers one such message at most)
+            self._h_store[at:at + ln].copy_(self.store[off:off + ln], non_blocking=True)
+            back[off] = at
+            at += ln
+        if stored:
+            stream.synchronize()
+            self.store_copies += len(stored)
+        hdst, hctl, hst = f._h["dst"].numpy(), f._h["ctl"].numpy(), self._h_store.numpy()
+        out = {}
+        for i, c in enumerate(conns):
+            units = []
+            for e in recs[i]:
+                off, ln, where = int(e["off"]), int(e["len"]), int(e["where"])
+                if where == _lib.FWS_JOIN_IN_CTL:
+                    units.append((int(e["opcode"]), hctl[off:off + ln].tobytes(), False))
+                elif where == _lib.FWS_JOIN_IN_DST:
+                    units.append((int(e["opcode"]), hdst[off:off + ln].tobytes(), bool(e["utf8_ok"])))
+                elif where == _lib.FWS_JOIN_IN_STORE:
+                    units.append((int(e["opcode"]), hst[back[off]:back[off] + ln].tobytes(), bool(e["utf8_ok"])))
+                else:                                 # dropped: longer than a half
+                    units.append((int(e["opcode"]), None, bool(e["utf8_ok"])))
+            resume = int(mres[i]["resume_off"])
+            f._pending[c] = bufs[c][resume:]
+            f.status[c] = int(mres[i]["status"])
+            out[c] = (units, resume)
+        return out
+
+    def feed(self, reads):
+        f = self.flow
+        for conn, data in reads.items():
+            if not 0 <= conn < f.n_conns:
+                raise ValueError(f"connection {conn} out of range")
+            if f.status[conn] not in (0, _lib.FWS_ERR_CAPACITY):
+                raise FwsError(f"MessageJoiner.feed after an error on connection {conn}", f.status[conn])
+            if len(data) > f.max_read:
+                raise ValueError(f"a read of {len(data)} bytes exceeds max_read = {f.max_read}")
+        bufs = {c: f._pending[c] + bytes(reads[c]) for c in reads}
+        out = {c: [] for c in reads}
+        while bufs:
+            again = {}
+            for c, (units, resume) in self._call(bufs).items():
+                out[c] += units
+                # more headers than one call takes: the rest of the same bytes, from resume_off, joined as well
+                if f.status[c] == _lib.FWS_ERR_CAPACITY and resume > 0 and f._pending[c]:
+                    again[c] = f._pending[c]
+            bufs = again
+        return out

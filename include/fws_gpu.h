@@ -1082,6 +1082,128 @@ int fws_gpu_reply_messages_strict_client(fws_gpu_ctx *ctx,
                                          fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns,
                                          uint32_t flags, const uint32_t *dev_keys, void *stream);
 
+/* ---- messages that span reads, joined on the device ------------------------------
+ * The decode calls deliver a message that arrives over several reads as parts:
+ * the open part of each call (open_off / open_len), then one FWS_MSG_CONTINUED
+ * entry whose off / len describe the last part only, each part in the read's
+ * region of dev_dst, which the next call overwrites. fws_gpu_join_messages puts
+ * the parts together in device memory, so that a consumer on the device -- a
+ * kernel that parses what arrives, a copy to the application's buffer -- sees
+ * every message as one contiguous run of bytes. It reads what
+ * fws_gpu_decode_messages_flow, _flow_client or _multi wrote for
+ * dev_reads[0..n), one workgroup per read, and changes nothing in it. */
+#define FWS_JOIN_IN_DST   0u   /* the message is whole in this read: dev_dst, not copied */
+#define FWS_JOIN_IN_STORE 1u   /* joined in the connection's slot of dev_store */
+#define FWS_JOIN_IN_CTL   2u   /* a control frame: dev_ctl */
+#define FWS_JOIN_NOWHERE  3u   /* dropped: longer than half a slot */
+#define FWS_JOIN_DROPPED  1u   /* fws_join_info.flags */
+
+typedef struct fws_join_state {  /* device memory, one per connection; all zero = new */
+    uint32_t open_opcode;        /* 0: none open; 1 / 2 */
+    uint32_t half;               /* 0 / 1: the half of the slot the open (or next) joined message uses */
+    uint32_t dropped;            /* 1: the open message outgrew its half; its bytes are not kept */
+    uint32_t reserved0;          /* 0 */
+    uint64_t open_bytes;         /* bytes of the open message seen so far, all calls */
+    uint64_t fill;               /* bytes of it in the half (== open_bytes, or 0 when dropped) */
+} fws_join_state;                /* 32 bytes */
+
+typedef struct fws_join_info {   /* one per decode entry, same index */
+    uint64_t off;                /* from the base of the buffer `where` names (absolute, not per read) */
+    uint64_t len;                /* the whole message, all its parts */
+    uint8_t opcode, utf8_ok, where, flags;
+    uint32_t reserved0;
+    uint64_t reserved;
+} fws_join_info;                 /* 32 bytes */
+
+typedef struct fws_join_result {
+    int32_t status;
+    uint32_t n_joined;           /* records written */
+    uint64_t copied;             /* bytes this read put into dev_store */
+    uint32_t open_opcode;        /* the state after the read */
+    uint32_t dropped;
+    uint64_t reserved;
+} fws_join_result;               /* 32 bytes */
+
+/* dev_reads, n, max_len, dev_msgs, dev_dst and dev_msg_results are the decode
+ * call's own arguments; the call only reads them.
+ *   slots     connection c's slot is dev_store + c * store_stride: two halves of
+ *             H = store_stride / 2 bytes. A message of more than H bytes is
+ *             dropped (below); a server that runs fws_gpu_reply_messages_strict
+ *             with 0 < max_message_bytes <= H has already answered it with 1009.
+ *   records   dev_joined[msg_base + i] describes entry dev_msgs[msg_base + i], i <
+ *             n_msgs. A FWS_JOIN_IN_STORE message stays valid until the next
+ *             fws_gpu_join_messages call that names the connection; a
+ *             FWS_JOIN_IN_DST or FWS_JOIN_IN_CTL message as long as the decode's
+ *             regions do.
+ * Per read r (conn = dev_reads[r].conn, S = dev_states[conn]), the entries in
+ * order, then the open part:
+ *   1. a control entry: where = FWS_JOIN_IN_CTL, off = ctl_off + entry.off, len,
+ *      opcode (utf8_ok 0). Nothing is copied.
+ *   2. a data entry without FWS_MSG_CONTINUED: where = FWS_JOIN_IN_DST, off =
+ *      dst_off + entry.off, len, opcode, utf8_ok. Nothing is copied.
+ *   3. the data entry with FWS_MSG_CONTINUED (at most one, the read's first data
+ *      entry): dev_dst[dst_off, dst_off + entry.len) is appended. Then, if
+ *      S.dropped: where = FWS_JOIN_NOWHERE, off = 0, len = S.open_bytes, flags =
+ *      FWS_JOIN_DROPPED, S.half unchanged; else where = FWS_JOIN_IN_STORE, off =
+ *      conn * store_stride + S.half * H, len = S.fill, and S.half ^= 1. Either
+ *      way opcode and utf8_ok are the entry's (the verdict on the whole message)
+ *      and open_opcode, dropped, open_bytes and fill become 0.
+ *   4. the open part, when fws_msg_result.open_opcode != 0: if S.open_opcode == 0
+ *      a new message starts (S.open_opcode = open_opcode, dropped = open_bytes =
+ *      fill = 0); then dev_dst[dst_off + open_off, + open_len) is appended
+ *      (open_len may be 0).
+ *   append p bytes: S.open_bytes += p; if S.dropped nothing is copied; else if
+ *      S.fill + p > H then S.dropped = 1, S.fill = 0 and nothing of this part is
+ *      copied; else the part goes to slot + S.half * H + S.fill and S.fill += p.
+ * The half toggles when a joined message is delivered, so the message rule 3
+ * delivers stays intact while rule 4 starts the next one in the other half, in
+ * the same read.
+ *   bytes     dev_store is written only inside the appended ranges: no byte
+ *             before fill, no byte of the other half, no byte of another
+ *             connection's slot. Loads touch only the 16-B aligned chunks of
+ *             dev_dst that hold at least one byte of a part.
+ *   nothing to do  status 0, n_joined 0, copied 0, the state untouched (the result's
+ *             open_opcode / dropped echo it): the reply calls' "no frames" tests --
+ *             the read's fws_msg_result.status is FWS_ERR_DECLINED or
+ *             FWS_ERR_INVALID, or its decode delivered nothing (n_msgs > msg_cap,
+ *             data_bytes > dst_cap or ctl_bytes > ctl_cap, the capacities taken
+ *             from the read's descriptor). Every other status (0, a protocol or
+ *             sequencing error, a frame-count FWS_ERR_CAPACITY) leaves a valid
+ *             prefix, and that prefix is joined.
+ *   refusals  per read; the call still returns 0, only the read's result is
+ *             written (other fields zero), the state and dev_store are untouched.
+ *             Tested in this order, before any store:
+ *               FWS_ERR_INVALID   conn >= n_conns (before the "nothing to do" tests)
+ *               FWS_ERR_INVALID   n_msgs > FWS_MSG_MULTI_MAX_FRAMES + 1
+ *               FWS_ERR_INVALID   a data entry or the open part over
+ *                                 FWS_MSG_MULTI_MAX_READ bytes, or S.open_opcode
+ *                                 not 0, 1 or 2
+ *               FWS_ERR_INVALID   decode and join out of step: a CONTINUED entry
+ *                                 with S.open_opcode == 0; a CONTINUED entry that
+ *                                 is not the first data entry; S.open_opcode != 0,
+ *                                 no CONTINUED entry, and a data entry present or
+ *                                 open_opcode != S.open_opcode
+ *             A dropped message is not an error. Two reads of one call that name
+ *             the same conn are a contract violation, as everywhere else.
+ *   max_len   the decode call's value; it selects the workgroup form as there.
+ *   ordering  stream-ordered: no host synchronisation, no copy, no allocation, no
+ *             workspace. The call is queued behind its decode call and in front
+ *             of the connection's next one, on either side of a reply call (both
+ *             only read the decode's output). Calls chain through dev_states.
+ * n == 0 returns 0 and looks at nothing. Otherwise ctx and every pointer must be
+ * non-null, dev_dst and dev_store 16-B aligned, max_len between 1 and
+ * FWS_MSG_MULTI_MAX_READ and store_stride a multiple of 32, at least 32, or the
+ * call returns FWS_ERR_INVALID before any device call. Out of scope: joining
+ * inside the decode kernels, a slot size per connection, echoing joined
+ * messages, the C++ adapter and the FLoop hook. */
+int fws_gpu_join_messages(fws_gpu_ctx *ctx,
+                          const fws_msg_read *dev_reads, uint32_t n, uint32_t max_len,
+                          const fws_msg_info *dev_msgs, const void *dev_dst,
+                          const fws_msg_result *dev_msg_results,
+                          void *dev_store, uint64_t store_stride,
+                          fws_join_info *dev_joined, fws_join_result *dev_results,
+                          fws_join_state *dev_states, uint32_t n_conns, void *stream);
+
 /* Host-memory send for one connection: WSocket::SendFrame (w_socket.h:832-944)
  * for its next n frames, in order. Frame i = payloads[i][0..lens[i]) of
  * WSTxFrameType frame_types[i] with last_frame_if_possible = last[i]; a client

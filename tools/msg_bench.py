@@ -87,6 +87,23 @@ usage: python tools/msg_bench.py [--target MiB] [--rounds R] [--steps K] [--out 
        python tools/msg_bench.py --tx-multi [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
        python tools/msg_bench.py --reply --parent-lib SO [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
 
+--join measures fws_gpu_join_messages: n connections (64, 512,
+4096) each receive one masked BIN message of two parts of 4 KiB (or 64 KiB) in
+two reads, the cut inside the frame's payload.
+  (i)  the loop, host wall time per step (both reads): flow decode -> copy back
+       results, entries and dst -> synchronise -> the host keeps / joins the parts
+       (two block copies: the least a host can do), all calls from a library built
+       from the parent commit (--parent-lib; two contexts give the A/A spread),
+       against this tree's decode -> join -> copy back results and records ->
+       synchronise. The store is compared with the host's joined bytes first.
+  (ii) the kernel alone, HIP events around back-to-back launches through raw
+       pointers: the pair of join launches (the open part, then the part that
+       completes the message), a device-to-device copy of the same bytes, and
+       the empty call -- reads that hold one whole message, nothing to copy --
+       against fws_gpu_reply_messages_multi with flags 0 on the same reads, the
+       launch floor of a sibling, timed twice per round for its spread.
+       python tools/msg_bench.py --join --parent-lib SO [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
+
 --reply-strict measures fws_gpu_reply_messages_strict: the
 echo of --reply (ii) with no failing item, n in {64, 512, 4096} x 4 KiB and 512
 x 64 KiB, and one row where every read is a CLOSE of one byte and fails. HIP
@@ -926,6 +943,176 @@ def reply_bench(n, size, parent_lib, rounds, steps, loop=True):
     return out
 
 
+def join_bench(n, part, parent_lib, rounds, steps, loop=True):
+    """--join: see the module docstring. part: the bytes of each of a message's two parts."""
+    dev = torch.device("cuda:0")
+    P = C.CDLL(parent_lib)
+    for name, res_t, args in _lib.SIGNATURES:
+        if hasattr(P, name):
+            getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
+    assert not hasattr(P, "fws_gpu_join_messages"), "--parent-lib is this tree's library"
+    L = _lib.lib()
+    rng = np.random.default_rng(37 * n + part)
+    size = 2 * part
+    hl = len(header(2, 1, size, 0))
+    body = rng.integers(0, 256, (min(n, 64), size), dtype=np.uint8)
+    keys = [int(rng.integers(0, 1 << 32)) for _ in range(min(n, 64))]
+    # read A: the header and the first part; read B: the second part; read W: a whole message of one part's size
+    hw = len(header(2, 1, part, 0))
+    lens = {"A": hl + part, "B": part, "W": hw + part}
+    slot = (hl + part + 15) & ~15
+    u8 = dict(dtype=torch.uint8, device=dev)
+    pin = dict(dtype=torch.uint8, pin_memory=True)
+    cap, ctl_cap = 2, 16
+    sets = {}
+    for name, ln in lens.items():
+        host = np.zeros((n, slot), dtype=np.uint8)
+        for r in range(n):
+            kb = np.resize(np.frombuffer(struct.pack("<I", keys[r % 64]), dtype=np.uint8), size)
+            msg = np.concatenate([np.frombuffer(header(2, 1, size, keys[r % 64]), dtype=np.uint8), body[r % 64] ^ kb])
+            if name == "W":
+                msg = np.concatenate([np.frombuffer(header(2, 1, part, keys[r % 64]), dtype=np.uint8),
+                                      (body[r % 64] ^ kb)[:part]])
+            host[r, :ln] = msg[hl + part:] if name == "B" else msg[:ln]
+        desc = np.zeros(n, dtype=_lib.MSG_READ)
+        for r in range(n):
+            desc[r] = (r * slot, r * slot, r * ctl_cap, ln, r, slot, ctl_cap, r * cap, cap, r * cap, cap, 0)
+        sets[name] = dict(len=ln, wire=torch.from_numpy(host.reshape(-1)).to(dev),
+                          reads=torch.from_numpy(desc.view(np.uint8).copy()).to(dev), dst=torch.zeros(n * slot, **u8),
+                          ctl=torch.zeros(n * ctl_cap, **u8), frames=torch.zeros(n * cap * 24, **u8),
+                          msgs=torch.zeros(n * cap * 32, **u8), res=torch.zeros(n * 40, **u8),
+                          mres=torch.zeros(n * 64, **u8), joined=torch.zeros(n * cap * 32, **u8),
+                          jres=torch.zeros(n * 32, **u8))
+    flows = {k: torch.zeros(n * _lib.MSG_FLOW.itemsize, **u8) for k in ("new", "old", "whole")}
+    H = (size + 15) & ~15
+    store = torch.zeros(n * 2 * H, **u8)
+    jstates = {k: torch.zeros(n * 32, **u8) for k in ("new", "whole")}
+    ctx = gpu.Ctx(0)
+    s = torch.cuda.current_stream()
+    pctx = []
+    for _ in range(2):
+        h = C.c_void_p()
+        assert P.fws_gpu_ctx_create(0, C.byref(h)) == 0
+        pctx.append(h)
+
+    def decode(fn, h, name, fl):
+        t = sets[name]
+        assert fn(h, t["wire"].data_ptr(), t["reads"].data_ptr(), n, t["len"], t["frames"].data_ptr(),
+                  t["msgs"].data_ptr(), t["dst"].data_ptr(), t["ctl"].data_ptr(), t["res"].data_ptr(),
+                  t["mres"].data_ptr(), flows[fl].data_ptr(), n, s.cuda_stream) == 0
+
+    def join(name, st):
+        t = sets[name]
+        assert L.fws_gpu_join_messages(ctx.h, t["reads"].data_ptr(), n, t["len"], t["msgs"].data_ptr(),
+                                       t["dst"].data_ptr(), t["mres"].data_ptr(), store.data_ptr(), 2 * H,
+                                       t["joined"].data_ptr(), t["jres"].data_ptr(), jstates[st].data_ptr(), n,
+                                       s.cuda_stream) == 0
+
+    # the parent's loop: every read's results, entries and dst come back and the host keeps the parts
+    h_mres, h_msgs, h_dst = torch.zeros(n * 64, **pin), torch.zeros(n * cap * 32, **pin), torch.zeros(n * slot, **pin)
+    v_mres, v_dst = h_mres.numpy().view(_lib.MSG_RESULT), h_dst.numpy().reshape(n, slot)
+    v_msgs = h_msgs.numpy().view(_lib.MSG_INFO).reshape(n, cap)
+    kept = np.zeros((n, part), dtype=np.uint8)
+    host_joined = np.zeros((n, size), dtype=np.uint8)
+
+    def old_loop(h):
+        def f(i):
+            for name in "AB":
+                decode(P.fws_gpu_decode_messages_flow, h, name, "old")
+                t = sets[name]
+                h_mres.copy_(t["mres"], non_blocking=True)
+                h_msgs.copy_(t["msgs"], non_blocking=True)
+                h_dst.copy_(t["dst"], non_blocking=True)
+                s.synchronize()
+                assert (v_mres["status"] == 0).all()
+                if name == "A":                          # the open part of every read (vectorised: same offsets)
+                    assert (v_mres["open_len"] == part).all() and (v_mres["open_off"] == 0).all()
+                    kept[:] = v_dst[:, :part]
+                else:                                    # the CONTINUED entry completes it
+                    assert (v_msgs[:, 0]["flags"] == 1).all() and (v_msgs[:, 0]["len"] == part).all()
+                    host_joined[:, :part] = kept
+                    host_joined[:, part:] = v_dst[:, :part]
+        return f
+
+    h_jres, h_joined = torch.zeros(n * 32, **pin), torch.zeros(n * cap * 32, **pin)
+    v_jres = h_jres.numpy().view(_lib.JOIN_RESULT)
+
+    def new_loop(i):
+        for name in "AB":
+            decode(L.fws_gpu_decode_messages_flow, ctx.h, name, "new")
+            join(name, "new")
+            h_jres.copy_(sets[name]["jres"], non_blocking=True)
+            h_joined.copy_(sets[name]["joined"], non_blocking=True)
+            s.synchronize()
+            assert (v_jres["status"] == 0).all()
+
+    # checked first: the store holds what the host joins
+    old_loop(pctx[0])(0)
+    new_loop(0)
+    rec = h_joined.numpy().view(_lib.JOIN_INFO).reshape(n, cap)[:, 0]
+    assert (rec["where"] == _lib.FWS_JOIN_IN_STORE).all() and (rec["len"] == size).all()
+    assert (rec["off"] == np.arange(n, dtype=np.uint64) * np.uint64(2 * H)).all()
+    got = store.cpu().numpy().reshape(n, 2 * H)[:, :size]
+    assert np.array_equal(got, host_joined) and np.array_equal(got[:len(body)], body)
+    # the whole-message reads for the empty call: decoded once, every record IN_DST, nothing copied
+    decode(L.fws_gpu_decode_messages_flow, ctx.h, "W", "whole")
+    join("W", "whole")
+    s.synchronize()
+    w = sets["W"]
+    jr = np.frombuffer(w["jres"].cpu().numpy().tobytes(), dtype=_lib.JOIN_RESULT)
+    assert (jr["status"] == 0).all() and (jr["n_joined"] == 1).all() and (jr["copied"] == 0).all()
+    tres, conns = torch.zeros(n * _lib.TX_RESULT.itemsize, **u8), torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
+    rstates, regions = torch.zeros(n * _lib.REPLY_STATE.itemsize, **u8), np.zeros(n, dtype=_lib.REPLY_REGION)
+    regions["out_off"], regions["out_cap"] = np.arange(n, dtype=np.uint64) * np.uint64(slot + 16), slot + 16
+    d_regions, out = torch.from_numpy(regions.view(np.uint8).copy()).to(dev), torch.zeros(n * (slot + 16), **u8)
+
+    def f_reply0(i):
+        assert L.fws_gpu_reply_messages_multi(ctx.h, w["reads"].data_ptr(), n, w["len"], w["msgs"].data_ptr(),
+                                              w["dst"].data_ptr(), w["ctl"].data_ptr(), w["mres"].data_ptr(),
+                                              d_regions.data_ptr(), out.data_ptr(), None, tres.data_ptr(),
+                                              conns.data_ptr(), rstates.data_ptr(), n, 0, s.cuda_stream) == 0
+
+    def f_copy(i):                                       # the same bytes device to device: a bandwidth reference
+        for name in "AB":
+            store.view(n, 2 * H)[:, :part].copy_(sets[name]["dst"].view(n, slot)[:, :part])
+
+    def f_join_ab(i):                                    # two launches: an open part, then the part that completes
+        join("A", "new")
+        join("B", "new")
+
+    out_line = {"measure": "join", "n": n, "part_bytes": part, "form": "small" if lens["A"] <= (16 << 10) else "full",
+                "copied_bytes_per_launch": n * part, "rounds": rounds, "steps": steps,
+                "device": torch.cuda.get_device_name(0), "parent_lib": os.path.basename(parent_lib)}
+    forms = {}
+    if loop:
+        forms.update({"loop_parent_a": (walled, old_loop(pctx[0])), "loop_parent_b": (walled, old_loop(pctx[1])),
+                      "loop_join": (walled, new_loop)})
+    forms.update({"k_join_pair": (timed, f_join_ab), "k_join_empty": (timed, lambda i: join("W", "whole")),
+                  "k_reply_no_frames_a": (timed, f_reply0), "k_reply_no_frames_b": (timed, f_reply0),
+                  "copy_pair": (timed, f_copy)})
+    times = {k: [] for k in forms}
+    for rnd in range(rounds):
+        for k in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[k].append(forms[k][0](forms[k][1], steps))
+    for k in forms:
+        out_line[k + "_us"] = round(statistics.median(times[k]), 2)
+        out_line[k + "_us_min_max"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+    if loop:                                             # a step is both reads of the message
+        base = min(out_line["loop_parent_a_us"], out_line["loop_parent_b_us"])
+        out_line["loop_aa_spread_us"] = round(abs(out_line["loop_parent_a_us"] - out_line["loop_parent_b_us"]), 2)
+        out_line["loop_parent_over_join"] = round(base / out_line["loop_join_us"], 2)
+    out_line["k_join_us_per_launch"] = round(out_line["k_join_pair_us"] / 2, 2)
+    out_line["k_join_gb_s"] = round(2 * n * part / out_line["k_join_pair_us"] / 1e3, 2)     # bytes copied (read + written once)
+    out_line["copy_gb_s"] = round(2 * n * part / out_line["copy_pair_us"] / 1e3, 2)
+    out_line["k_sibling_spread_us"] = round(abs(out_line["k_reply_no_frames_a_us"] - out_line["k_reply_no_frames_b_us"]), 2)
+    out_line["k_join_empty_minus_sibling_us"] = round(
+        out_line["k_join_empty_us"] - min(out_line["k_reply_no_frames_a_us"], out_line["k_reply_no_frames_b_us"]), 2)
+    for h in pctx:
+        P.fws_gpu_ctx_destroy(h)
+    ctx.close()
+    return out_line
+
+
 def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
     """--reply-strict: see the module docstring. size: the message's payload
     bytes; fail: every read is a CLOSE frame of one byte instead, which the
@@ -1399,9 +1586,23 @@ def main():
                     help="measure the masked (client) reply calls and the server calls against the parent's (see above)")
     ap.add_argument("--flow-client", action="store_true",
                     help="measure fws_gpu_decode_messages_flow_client and the server call against the parent's")
+    ap.add_argument("--join", action="store_true", help="measure fws_gpu_join_messages (see above)")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.join:
+        assert a.parent_lib, "--join needs --parent-lib"
+        grid_n = "64,512,4096" if a.grid_n == ap.get_default("grid_n") else a.grid_n
+        grid_kib = "4,64" if a.grid_kib == ap.get_default("grid_kib") else a.grid_kib
+        for kib in map(int, grid_kib.split(",")):
+            for n in map(int, grid_n.split(",")):
+                lines.append(json.dumps(join_bench(n, kib << 10, os.path.abspath(a.parent_lib), a.rounds, a.steps,
+                                                   loop=kib == 4)))
+                print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.reply_client or a.flow_client:
         assert a.parent_lib, "--reply-client / --flow-client need --parent-lib"
         lib = os.path.abspath(a.parent_lib)
