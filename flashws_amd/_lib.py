@@ -122,6 +122,11 @@ JOIN_INFO = np.dtype([("off", "<u8"), ("len", "<u8"), ("opcode", "u1"), ("utf8_o
 JOIN_RESULT = np.dtype([("status", "<i4"), ("n_joined", "<u4"), ("copied", "<u8"), ("open_opcode", "<u4"),
                         ("dropped", "<u4"), ("reserved", "<u8")])
 assert JOIN_STATE.itemsize == 32 and JOIN_INFO.itemsize == 32 and JOIN_RESULT.itemsize == 32
+# fws_gpu_publish_messages: the records one subscriber's list may name and a subscriber's descriptor
+FWS_PUB_MAX_ITEMS = 256
+PUB_SUB = np.dtype([("out_off", "<u8"), ("out_cap", "<u4"), ("conn", "<u4"), ("list_off", "<u4"), ("list_len", "<u4"),
+                    ("frame_base", "<u4"), ("frame_cap", "<u4")])
+assert PUB_SUB.itemsize == 32
 
 
 def close_code_valid(code):
@@ -208,6 +213,8 @@ SIGNATURES = [
     ("fws_gpu_reply_messages_strict_client", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P,
                                                   _P, _P, _U32, _U32, _P, _P]),
     ("fws_gpu_join_messages", _I, [_P, _P, _U32, _U32, _P, _P, _P, _P, _U64, _P, _P, _P, _U32, _P]),
+    ("fws_gpu_publish_messages", _I, [_P, _P, _U32, _P, _P, _P, _P, _U32, _P, _U32, _U32, _P, _P, _P, _P, _P, _U32,
+                                      _P]),
     ("fws_tx_session_create", _I, [_P, _I, C.POINTER(C.c_void_p)]),
     ("fws_tx_session_destroy", None, [_P]),
     ("fws_tx_session_send", _I, [_P, _P, _P, _P, _P, _P, _U32, _P, _U64, _PU64]),

@@ -654,6 +654,24 @@ int fws_gpu_join_messages(fws_gpu_ctx *ctx, const fws_msg_read *dev_reads, uint3
                            (hipStream_t)stream);
 }
 
+int fws_gpu_publish_messages(fws_gpu_ctx *ctx, const fws_join_info *dev_msgs, uint32_t n_msgs, const void *dev_dst,
+                             const void *dev_store, const void *dev_ctl, const uint32_t *dev_list, uint32_t n_list,
+                             const fws_pub_sub *dev_subs, uint32_t n, uint32_t max_len, void *dev_out,
+                             fws_frame_info *dev_frames, fws_tx_result *dev_results, fws_tx_conn *dev_conns,
+                             fws_reply_state *dev_states, uint32_t n_conns, void *stream) {
+    if (n == 0) return 0;
+    // (dev_dst, dev_store and dev_ctl may be null: a record that names a null base refuses its subscriber;
+    // dev_frames may be null: a subscriber with frame_cap 0 writes no record)
+    if (!ctx || !dev_msgs || !dev_list || !dev_subs || !dev_out || !dev_results || !dev_conns || !dev_states)
+        return FWS_ERR_INVALID;
+    if (((uintptr_t)dev_out & 15u) != 0) return FWS_ERR_INVALID;
+    if (max_len < 1u || max_len > FWS_TX_MULTI_MAX_SEND) return FWS_ERR_INVALID;
+    if (int r = fws_hip_status(hipSetDevice(ctx->device))) return r;
+    return fws_launch_publish(dev_msgs, n_msgs, (const uint8_t *)dev_dst, (const uint8_t *)dev_store,
+                              (const uint8_t *)dev_ctl, dev_list, n_list, dev_subs, n, max_len, (uint8_t *)dev_out,
+                              dev_frames, dev_results, dev_conns, dev_states, n_conns, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 int fws_decode_prepare(fws_gpu_ctx *ctx, uint64_t len, uint32_t cap, bool utf8) {

@@ -385,6 +385,12 @@ int fws_launch_join(const fws_msg_read *reads, uint32_t n, uint32_t max_len, con
                     const uint8_t *dst, const fws_msg_result *mres, uint8_t *store, uint64_t store_stride,
                     fws_join_info *joined, fws_join_result *res, fws_join_state *states, uint32_t n_conns,
                     hipStream_t s);
+// fws_gpu_publish_messages (publish_kernels.hip): the listed messages of n subscribers as server frames, one
+// workgroup per subscriber; no workspace
+int fws_launch_publish(const fws_join_info *msgs, uint32_t n_msgs, const uint8_t *dst, const uint8_t *store,
+                       const uint8_t *ctl, const uint32_t *list, uint32_t n_list, const fws_pub_sub *subs, uint32_t n,
+                       uint32_t max_len, uint8_t *out, fws_frame_info *frames, fws_tx_result *res, fws_tx_conn *conns,
+                       fws_reply_state *states, uint32_t n_conns, hipStream_t s);
 int fws_launch_msg_ctl(fws_gpu_ctx *ctx, const uint8_t *wire, const fws_frame_info *frames, uint32_t cap,
                        const uint32_t *n_dev, const fws_msg_result *res, uint8_t *ctl, uint64_t ctl_cap,
                        hipStream_t s, const uint32_t *deny = nullptr);

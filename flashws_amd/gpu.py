@@ -1453,3 +1453,125 @@ class MessageJoiner:
                     again[c] = f._pending[c]
             bufs = again
         return out
+
+
+def publish_messages(ctx, msgs, n_msgs, dst, store, ctl, lst, n_list, subs, n, max_len, out, frames, results, conns,
+                     states, n_conns, stream=None):
+    """fws_gpu_publish_messages: the listed messages of n subscribers written as
+    server frames in one launch. msgs holds n_msgs fws_join_info records
+    (_lib.JOIN_INFO: what join_messages wrote, or the application's own), dst /
+    store / ctl the buffers their `where` names (None where no record names
+    it), lst n_list uint32 indices into msgs, subs n fws_pub_sub
+    (_lib.PUB_SUB), results n fws_tx_result, conns n_conns fws_tx_conn (the
+    array encode_messages_multi and the reply calls take), states n_conns
+    fws_reply_state; frames may be None when every frame_cap is 0. Returns the
+    call's status; nothing is synchronised."""
+    opt = lambda t: _ptr(t) if t is not None else None   # noqa: E731
+    return lib().fws_gpu_publish_messages(ctx.h, _ptr(msgs), n_msgs, opt(dst), opt(store), opt(ctl), _ptr(lst), n_list,
+                                          _ptr(subs), n, max_len, _ptr(out), opt(frames), _ptr(results), _ptr(conns),
+                                          _ptr(states), n_conns, _stream_handle(stream))
+
+
+class MessagePublisher:
+    """Fan-out for a server: publish(messages, lists) with messages = [(opcode,
+    bytes), ...] and lists = {conn: [index, ...]} writes, for every connection
+    named, the frames of its listed messages in list order -- one upload (the
+    payloads, their records, the lists and the subscribers in one block), one
+    fws_gpu_publish_messages call and one synchronisation -- and returns {conn:
+    wire bytes}. Equal lists are uploaded once and shared by their subscribers.
+    A refused subscriber raises FwsError with its status (the other
+    subscribers' frames of that call are written and counted all the same).
+    max_out is a connection's region: the most wire bytes one publish may give
+    it. conns / states: the fws_tx_conn / fws_reply_state tensors of a
+    MessageSender (sender.conns) or MessageResponder to sequence one
+    connection's frames through one state; by default the publisher owns zeroed
+    ones. calls counts the launches."""
+
+    def __init__(self, ctx, n_conns, max_out, device="cuda:0", conns=None, states=None):
+        if max_out < 1:
+            raise ValueError("max_out must be at least 1")
+        self.ctx, self.n_conns = ctx, n_conns
+        self.out_slot = (int(max_out) + 15) & ~15
+        self.dev = torch.device(device)
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        pin = dict(dtype=torch.uint8, pin_memory=True)
+        self._sizes = dict(out=self.out_slot, res=_lib.TX_RESULT.itemsize)
+        self._d = {k: torch.zeros(n_conns * sz, **u8) for k, sz in self._sizes.items()}
+        self._h = {k: torch.zeros(n_conns * sz, **pin) for k, sz in self._sizes.items()}
+        self.conns = conns if conns is not None else torch.zeros(n_conns * _lib.TX_CONN.itemsize, **u8)
+        self.states = states if states is not None else torch.zeros(n_conns * _lib.REPLY_STATE.itemsize, **u8)
+        self._up_d = self._up_h = None                # the upload block, grown when a publish needs more
+        self.calls = 0
+        self.lists_uploaded = 0                       # distinct lists of the last publish
+
+    def _block(self, nbytes):
+        if self._up_d is None or self._up_d.numel() < nbytes:
+            size = max(4096, 1 << (nbytes - 1).bit_length())
+            self._up_d = torch.zeros(size, dtype=torch.uint8, device=self.dev)
+            self._up_h = torch.zeros(size, dtype=torch.uint8, pin_memory=True)
+        return self._up_h.numpy()
+
+    def publish(self, messages, lists):
+        conns = list(lists)
+        for c in conns:
+            if not 0 <= c < self.n_conns:
+                raise ValueError(f"connection {c} out of range")
+        if not conns:
+            return {}
+        messages = [(int(op), bytes(p)) for op, p in messages]
+        # the block: records | lists | subscribers | payloads, each part 16-B aligned
+        recs = np.zeros(len(messages), dtype=_lib.JOIN_INFO)
+        at = 0
+        for i, (op, p) in enumerate(messages):
+            recs[i]["off"], recs[i]["len"], recs[i]["opcode"] = at, len(p), op
+            recs[i]["where"], recs[i]["utf8_ok"] = _lib.FWS_JOIN_IN_DST, 1
+            at += len(p)
+        pay_len = at
+        where, flat = {}, []
+        for c in conns:
+            key = tuple(int(i) for i in lists[c])
+            if key not in where:
+                where[key] = len(flat)
+                flat += key
+        self.lists_uploaded = len(where)
+        lst = np.asarray(flat, dtype=np.uint32)
+        subs = np.zeros(len(conns), dtype=_lib.PUB_SUB)
+        for i, c in enumerate(conns):
+            key = tuple(int(x) for x in lists[c])
+            subs[i] = (i * self.out_slot, self.out_slot, c, where[key], len(key), 0, 0)
+        a16 = lambda v: (v + 15) & ~15                # noqa: E731
+        o_recs = 0
+        o_list = a16(o_recs + recs.nbytes)
+        o_subs = a16(o_list + lst.nbytes)
+        o_pay = a16(o_subs + subs.nbytes)
+        total = o_pay + max(16, pay_len)
+        h = self._block(total)
+        h[o_recs:o_recs + recs.nbytes] = recs.view(np.uint8)
+        h[o_list:o_list + lst.nbytes] = lst.view(np.uint8)
+        h[o_subs:o_subs + subs.nbytes] = subs.view(np.uint8)
+        at = o_pay
+        for _, p in messages:
+            h[at:at + len(p)] = np.frombuffer(p, dtype=np.uint8)
+            at += len(p)
+        stream = torch.cuda.current_stream(self.dev)
+        d = self._up_d
+        d[:total].copy_(self._up_h[:total], non_blocking=True)
+        n, sz = len(conns), self._sizes
+        max_len = max([1] + [len(p) for op, p in messages if op in (1, 2)])
+        check("fws_gpu_publish_messages",
+              publish_messages(self.ctx, d[o_recs:], len(messages), d[o_pay:], None, None, d[o_list:], len(lst),
+                               d[o_subs:], n, min(max_len, _lib.FWS_TX_MULTI_MAX_SEND), self._d["out"], None,
+                               self._d["res"], self.conns, self.states, self.n_conns, stream=stream))
+        self.calls += 1
+        for k in ("res", "out"):
+            self._h[k][:n * sz[k]].copy_(self._d[k][:n * sz[k]], non_blocking=True)
+        stream.synchronize()
+        res = np.frombuffer(self._h["res"].numpy()[:n * sz["res"]].tobytes(), dtype=_lib.TX_RESULT)
+        out = {}
+        for i, c in enumerate(conns):
+            if int(res[i]["status"]):
+                raise FwsError(f"fws_gpu_publish_messages refused the subscriber of connection {c}",
+                               int(res[i]["status"]))
+            o = i * self.out_slot
+            out[c] = self._h["out"].numpy()[o:o + int(res[i]["out_len"])].tobytes()
+        return out

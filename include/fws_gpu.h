@@ -1204,6 +1204,115 @@ int fws_gpu_join_messages(fws_gpu_ctx *ctx,
                           fws_join_info *dev_joined, fws_join_result *dev_results,
                           fws_join_state *dev_states, uint32_t n_conns, void *stream);
 
+/* ---- messages fanned out to many connections ------------------------------------
+ * Every call above is one-to-one: what came from or goes to connection c stays
+ * with connection c. fws_gpu_publish_messages is one-to-many: a set of messages
+ * in device memory, lists of them, and per receiving connection (a subscriber)
+ * one list and one region of dev_out, one workgroup per subscriber. A room's
+ * members all name the room's list; each gets the listed messages as server
+ * frames, back to back, several a call. The messages are fws_join_info records,
+ * the layout fws_gpu_join_messages writes, so what a join call delivered is
+ * published with no host in between; an application that publishes its own
+ * payloads fills such records itself: where = FWS_JOIN_IN_DST and off from the
+ * buffer it passes as dev_dst, FWS_JOIN_IN_STORE and dev_store, FWS_JOIN_IN_CTL
+ * and dev_ctl. utf8_ok, flags and the reserved fields are not looked at. */
+#define FWS_PUB_MAX_ITEMS 256u          /* records one subscriber's list may name */
+
+typedef struct fws_pub_sub {            /* device memory, one per receiving connection */
+    uint64_t out_off;                   /* its region of dev_out, 16-B aligned */
+    uint32_t out_cap;
+    uint32_t conn;                      /* index into dev_conns / dev_states, < n_conns; distinct within a call */
+    uint32_t list_off, list_len;        /* its items: dev_list[list_off .. list_off + list_len) */
+    uint32_t frame_base, frame_cap;     /* its slice of dev_frames (frame_cap 0: no records) */
+} fws_pub_sub;                          /* 32 bytes */
+
+/* dev_list holds n_list indices into dev_msgs[0..n_msgs); slices of it may be
+ * shared by any number of subscribers and may overlap. Per subscriber s (conn =
+ * dev_subs[s].conn, offsets relative to the region dev_out + out_off):
+ *   items     the listed records in list order. A record with opcode == 0 or
+ *             where == FWS_JOIN_NOWHERE is nothing: no frame, and not judged --
+ *             so a caller that zeroes dev_joined on the stream before the join
+ *             call may list every slot of a read's entry slice without knowing
+ *             n_msgs. Opcode 1 or 2: one data frame with that opcode, FIN = 1,
+ *             the whole message as payload (len 0: an empty frame). Opcode 9 or
+ *             10: one control frame, FIN = 1. Opcode 8: one CLOSE frame with the
+ *             record's payload; dev_states[conn].close_sent becomes 1, close_code
+ *             and fail_code stay what they were, and every later item of the
+ *             list is dropped (a server going away with 1001).
+ *   bytes     server frames (no MASK bit, no key) back to back from the region's
+ *             start, each what fws_gpu_encode_frames writes for that payload,
+ *             opcode and FIN. No byte outside [out_off, out_off + out_len) is
+ *             written, inside out_cap or not. Sources may have any alignment;
+ *             loads touch only the 16-B aligned chunks of a source that hold at
+ *             least one payload byte. Regions must not overlap each other or any
+ *             source.
+ *   state     on success dev_conns[conn] keeps last_msg_not_fin, frames +=
+ *             n_frames, wire_bytes += out_len; dev_states[conn] as above. The
+ *             result echoes last_msg_not_fin (as 0 / 1).
+ *   records   dev_frames[frame_base + j], j < min(n_frames, frame_cap), as the
+ *             reply calls write them (hdr_off relative to the region, key 0).
+ *             dev_frames may be NULL when every frame_cap is 0.
+ *   refusals  per subscriber; the call still returns 0, only the subscriber's
+ *             result is written (other fields zero except where stated), both
+ *             states and the region are untouched, and other subscribers are
+ *             not affected. Every listed record that is not nothing is judged,
+ *             dropped behind a CLOSE or not. The verdict is the first row that
+ *             applies to any of them:
+ *               FWS_ERR_INVALID        out_off not 16-B aligned, conn >= n_conns,
+ *                                      list_len > FWS_PUB_MAX_ITEMS, list_off +
+ *                                      list_len > n_list, an index >= n_msgs, an
+ *                                      opcode not 0, 1, 2, 8, 9 or 10, a where
+ *                                      above 3, a record (of any len) that names
+ *                                      a base passed as NULL
+ *               (no frames)            status 0, n_frames 0, out_len 0, the result
+ *                                      echoes last_msg_not_fin: close_sent is set,
+ *                                      or the list is empty or all nothing
+ *               FWS_ERR_CONTROL_FRAME  an opcode 8, 9 or 10 record over 125 bytes
+ *               FWS_ERR_DECLINED       a data record with len > max_len or len >
+ *                                      FWS_TX_MULTI_MAX_SEND: the host sends such a
+ *                                      message in pieces through
+ *                                      fws_gpu_encode_messages_multi
+ *               FWS_ERR_SEQUENCE       dev_conns[conn].last_msg_not_fin != 0 and a
+ *                                      data frame is among the frames that would
+ *                                      be written: the application is in the
+ *                                      middle of a fragmented send to this
+ *                                      connection, and a whole message must not
+ *                                      be cut into it. (The reference's SendFrame
+ *                                      would silently make it a continuation,
+ *                                      w_socket.h:845-848; this call refuses
+ *                                      instead.) A control-only list, or one
+ *                                      whose data records all lie behind a CLOSE,
+ *                                      goes through and leaves last_msg_not_fin
+ *                                      as it was.
+ *               FWS_ERR_CAPACITY       the bytes needed exceed out_cap; out_len =
+ *                                      the bytes needed, n_frames is set
+ *             Two subscribers of one call that name the same conn are a contract
+ *             violation: the result is undefined for that connection only.
+ *   max_len   the caller's bound on a data record's len, between 1 and
+ *             FWS_TX_MULTI_MAX_SEND. It selects the workgroup form as in the reply
+ *             calls: up to 16 KiB 256 threads, above 1024.
+ *   ordering  stream-ordered: no host synchronisation, no copy, no allocation, no
+ *             workspace. Calls queued on one stream chain through dev_conns and
+ *             dev_states; a publish call may stand on either side of a reply or
+ *             encode call that shares them.
+ * n == 0 returns 0 and looks at nothing. Otherwise ctx, dev_msgs, dev_list,
+ * dev_subs, dev_out, dev_results, dev_conns and dev_states must be non-null,
+ * dev_out 16-B aligned and max_len in range, or the call returns FWS_ERR_INVALID
+ * before any device call; dev_dst, dev_store, dev_ctl and dev_frames may be NULL.
+ * A region is at most FWS_PUB_MAX_ITEMS * (FWS_TX_MULTI_MAX_SEND + 10) bytes,
+ * below 2^26. Out of scope: cutting a message into several frames; masked
+ * (client) frames; leaving the sender out of its own room (the host builds the
+ * lists); dropping TEXT records with utf8_ok == 0; topic-major input (message ->
+ * subscribers) and its inversion on the device; the C++ adapter and the FLoop
+ * hook. */
+int fws_gpu_publish_messages(fws_gpu_ctx *ctx,
+                             const fws_join_info *dev_msgs, uint32_t n_msgs,
+                             const void *dev_dst, const void *dev_store, const void *dev_ctl,
+                             const uint32_t *dev_list, uint32_t n_list,
+                             const fws_pub_sub *dev_subs, uint32_t n, uint32_t max_len,
+                             void *dev_out, fws_frame_info *dev_frames, fws_tx_result *dev_results,
+                             fws_tx_conn *dev_conns, fws_reply_state *dev_states, uint32_t n_conns, void *stream);
+
 /* Host-memory send for one connection: WSocket::SendFrame (w_socket.h:832-944)
  * for its next n frames, in order. Frame i = payloads[i][0..lens[i]) of
  * WSTxFrameType frame_types[i] with last_frame_if_possible = last[i]; a client

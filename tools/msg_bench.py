@@ -104,6 +104,22 @@ two reads, the cut inside the frame's payload.
        launch floor of a sibling, timed twice per round for its spread.
        python tools/msg_bench.py --join --parent-lib SO [--grid-n N,..] [--grid-kib K,..] [--rounds R] [--out FILE]
 
+--publish measures fws_gpu_publish_messages: BIN messages in one
+source buffer fanned out to every member of their room, one region per member.
+  a  1 message of 4 KiB to 4,096 subscribers
+  b  1 message of 64 KiB to 1,024 subscribers
+  c  64 messages of 128 B to 4,096 subscribers (one list; seam-heavy)
+  d  8 rooms of 512 members, 4 messages of 1 KiB per room
+HIP events around back-to-back launches through raw pointers, at least 100 steps
+after 10 of warm-up, rotating four output arenas; within each round, alternating:
+the publish call; a device-to-device copy of one arena into the next (the same
+bytes written); and, for a and b, fws_gpu_encode_messages_multi of a library
+built from the parent commit (--parent-lib) on n one-frame server sends that
+share one src_off, in two contexts (the A/A spread). Every region is compared
+with the room's frames first, and with the parent's output. bytes_moved = the
+distinct source bytes once + the region bytes, held against 8 TB/s.
+       python tools/msg_bench.py --publish [--parent-lib SO] [--cases a,b,c,d] [--rounds R] [--steps S] [--out FILE]
+
 --reply-strict measures fws_gpu_reply_messages_strict: the
 echo of --reply (ii) with no failing item, n in {64, 512, 4096} x 4 KiB and 512
 x 64 KiB, and one row where every read is a CLOSE of one byte and fails. HIP
@@ -1113,6 +1129,119 @@ def join_bench(n, part, parent_lib, rounds, steps, loop=True):
     return out_line
 
 
+PUBLISH_CASES = {"a": dict(rooms=1, members=4096, msgs=1, size=4 << 10), "b": dict(rooms=1, members=1024, msgs=1, size=64 << 10),
+                 "c": dict(rooms=1, members=4096, msgs=64, size=128), "d": dict(rooms=8, members=512, msgs=4, size=1 << 10)}
+PUBLISH_ARENAS = 4
+
+
+def publish_bench(case, parent_lib, rounds, steps):
+    """--publish: see the module docstring."""
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    p = PUBLISH_CASES[case]
+    rooms, members, msgs, size = p["rooms"], p["members"], p["msgs"], p["size"]
+    n, n_msgs = rooms * members, rooms * msgs
+    rng = np.random.default_rng(ord(case))
+    frame = size + 2 + (0 if size < 126 else 2 if size <= 65535 else 8)
+    need = msgs * frame
+    slot = (need + 15) & ~15
+    u8 = dict(dtype=torch.uint8, device=dev)
+    src_h = rng.integers(0, 256, n_msgs * size, dtype=np.uint8)
+    src = torch.from_numpy(src_h).to(dev)
+    recs = np.zeros(n_msgs, dtype=_lib.JOIN_INFO)
+    for i in range(n_msgs):
+        recs[i]["off"], recs[i]["len"], recs[i]["opcode"], recs[i]["where"] = i * size, size, 2, _lib.FWS_JOIN_IN_DST
+    lst = np.arange(n_msgs, dtype=np.uint32)          # room r's list: its msgs records
+    subs = np.zeros(n, dtype=_lib.PUB_SUB)
+    for s in range(n):
+        subs[s] = (s * slot, slot, s, (s // members) * msgs, msgs, 0, 0)
+    d_recs, d_lst, d_subs = (torch.from_numpy(x.view(np.uint8).copy()).to(dev) for x in (recs, lst, subs))
+    outs = [torch.zeros(n * slot, **u8) for _ in range(PUBLISH_ARENAS)]
+    res, conns = torch.zeros(n * _lib.TX_RESULT.itemsize, **u8), torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
+    states = torch.zeros(n * _lib.REPLY_STATE.itemsize, **u8)
+    ctx = gpu.Ctx(0, max_frames=64, max_stream_bytes=4096)
+    h = torch.cuda.current_stream().cuda_stream
+    ptr = dict(recs=d_recs.data_ptr(), lst=d_lst.data_ptr(), subs=d_subs.data_ptr(), src=src.data_ptr(),
+               res=res.data_ptr(), conns=conns.data_ptr(), states=states.data_ptr(), outs=[o.data_ptr() for o in outs])
+    pub = L.fws_gpu_publish_messages
+
+    def f_publish(i):
+        assert pub(ctx.h, ptr["recs"], n_msgs, ptr["src"], None, None, ptr["lst"], n_msgs, ptr["subs"], n, size,
+                   ptr["outs"][i % PUBLISH_ARENAS], None, ptr["res"], ptr["conns"], ptr["states"], n, h) == 0
+
+    def f_copy(i):                                    # the same bytes moved by a device-to-device copy
+        outs[(i + 1) % PUBLISH_ARENAS].copy_(outs[i % PUBLISH_ARENAS])
+
+    # checked first: every region holds the room's frames
+    for i in range(PUBLISH_ARENAS):
+        f_publish(i)
+    torch.cuda.synchronize()
+    r_ = np.frombuffer(res.cpu().numpy().tobytes(), dtype=_lib.TX_RESULT)
+    assert (r_["status"] == 0).all() and (r_["out_len"] == need).all() and (r_["n_frames"] == msgs).all()
+    hdr = header(2, 1, size, 0)[:-4]                  # a server frame's: no key, no MASK bit
+    hdr = hdr[:1] + bytes([hdr[1] & 0x7F]) + hdr[2:]
+    for r in range(rooms):
+        want = b"".join(hdr + src_h[(r * msgs + j) * size:(r * msgs + j + 1) * size].tobytes() for j in range(msgs))
+        want = torch.from_numpy(np.frombuffer(want, dtype=np.uint8).copy()).to(dev)
+        for o in outs:
+            got = o.view(n, slot)[r * members:(r + 1) * members, :need]
+            assert torch.equal(got, want.expand(members, need)), "a region differs from the room's frames"
+    forms = {"publish": f_publish, "copy": f_copy}
+    parents = []
+    if msgs == 1 and rooms == 1 and parent_lib:
+        # the parent's way to the same bytes: n one-frame server sends that share one src_off
+        P = C.CDLL(parent_lib)
+        for name, res_t, args in _lib.SIGNATURES:
+            if hasattr(P, name):
+                getattr(P, name).restype, getattr(P, name).argtypes = res_t, args
+        assert not hasattr(P, "fws_gpu_publish_messages"), "--parent-lib is this tree's library"
+        sends = np.zeros(n, dtype=_lib.TX_SEND)
+        for s in range(n):
+            sends[s]["out_off"], sends[s]["len"], sends[s]["out_cap"], sends[s]["conn"] = s * slot, size, slot, s
+            sends[s]["frame_type"], sends[s]["last"] = 2, 1
+        d_sends = torch.from_numpy(sends.view(np.uint8).copy()).to(dev)
+        out_p = [torch.zeros(n * slot, **u8) for _ in range(PUBLISH_ARENAS)]
+        conns_p = torch.zeros(n * _lib.TX_CONN.itemsize, **u8)
+        for tag in ("a", "b"):
+            pc = C.c_void_p()
+            assert P.fws_gpu_ctx_create(0, C.byref(pc)) == 0
+            parents.append(pc)
+
+            def f_parent(i, pc=pc):
+                assert P.fws_gpu_encode_messages_multi(pc, out_p[i % PUBLISH_ARENAS].data_ptr(), ptr["src"],
+                                                       d_sends.data_ptr(), n, size, None, ptr["res"],
+                                                       conns_p.data_ptr(), n, h) == 0
+            forms["encode_parent_" + tag] = f_parent
+        for i in range(PUBLISH_ARENAS):
+            forms["encode_parent_a"](i)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(outs, out_p)), "the publish and the parent's encode differ"
+    times = {name: [] for name in forms}
+    for rnd in range(rounds):
+        for name in (list(forms) if rnd % 2 == 0 else list(forms)[::-1]):
+            times[name].append(timed(forms[name], steps))
+    moved = n_msgs * size + n * need                  # distinct source bytes once + region bytes
+    out = {"measure": "publish", "case": case, "subscribers": n, "rooms": rooms, "msgs_per_list": msgs,
+           "msg_bytes": size, "region_bytes": need, "form": "small" if size <= (16 << 10) else "full",
+           "bytes_moved": moved, "rounds": rounds, "steps": steps, "arenas": PUBLISH_ARENAS,
+           "device": torch.cuda.get_device_name(0), "parent_lib": os.path.basename(parent_lib) if parents else ""}
+    for name in forms:
+        out[name + "_us"] = round(statistics.median(times[name]), 2)
+        out[name + "_us_min_max"] = [round(min(times[name]), 2), round(max(times[name]), 2)]
+    out["publish_tb_s"] = round(moved / out["publish_us"] / 1e6, 3)
+    out["publish_of_8tb_s_roofline"] = round(moved / out["publish_us"] / 1e6 / 8.0, 3)
+    out["publish_over_copy"] = round(out["publish_us"] / out["copy_us"], 2)
+    if parents:
+        pa, pb = out["encode_parent_a_us"], out["encode_parent_b_us"]
+        out["parent_spread_us"] = round(abs(pa - pb), 2)
+        out["publish_minus_parent_us"] = round(out["publish_us"] - min(pa, pb), 2)
+        out["publish_over_parent"] = round(out["publish_us"] / min(pa, pb), 3)
+        for pc in parents:
+            P.fws_gpu_ctx_destroy(pc)
+    ctx.close()
+    return out
+
+
 def reply_strict_bench(n, size, parent_lib, rounds, steps, fail=False):
     """--reply-strict: see the module docstring. size: the message's payload
     bytes; fail: every read is a CLOSE frame of one byte instead, which the
@@ -1587,9 +1716,20 @@ def main():
     ap.add_argument("--flow-client", action="store_true",
                     help="measure fws_gpu_decode_messages_flow_client and the server call against the parent's")
     ap.add_argument("--join", action="store_true", help="measure fws_gpu_join_messages (see above)")
+    ap.add_argument("--publish", action="store_true", help="measure fws_gpu_publish_messages (see above)")
+    ap.add_argument("--cases", default="a,b,c,d", help="--publish: the cases to run")
     a = ap.parse_args()
     target = a.target << 20
     lines = []
+    if a.publish:
+        for case in a.cases.split(","):
+            lines.append(json.dumps(publish_bench(case, os.path.abspath(a.parent_lib) if a.parent_lib else "",
+                                                  a.rounds, max(a.steps, 100))))
+            print(lines[-1], flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.join:
         assert a.parent_lib, "--join needs --parent-lib"
         grid_n = "64,512,4096" if a.grid_n == ap.get_default("grid_n") else a.grid_n
